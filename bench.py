@@ -7,6 +7,12 @@ up to 10 re-integration queue ops and GC; per submap one local solve (11 frames,
 trajectory update that feeds the queue). W warmup submaps run untimed, then K submaps are timed.
 Every input (frames, cache frames, correspondences) is resident in HBM before timing starts.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, runs the untimed prefix, times the K submaps and prints
+the result line: the headline figure, ms_per_step and what the timed loop's own counters give. `--dump-outputs
+DIR` also writes the loop's outputs after the last timed step (dump_outputs). Everything below (render window,
+standalone global solve, end-of-sequence phase, rooflines, shard balance, raycast, marching cubes, CPU baseline)
+takes work of its own and is measured and added to the line only with `--full`.
+
 Multi-GPU (torchrun, one process per GPU): the TSDF is sharded by 1 m chunk ownership
 (every GPU sees every frame and integrates only the blocks it owns, no
 collective); local BA solves run round-robin by submap with an RCCL broadcast of the solved poses;
@@ -334,6 +340,58 @@ def roofline_ba(solo):
                     "formula: the iteration is bound by its two hand-offs (Ap to the finisher, p back), not HBM"}
 
 
+DUMP_VIEWS = 4  # renders of the final scene in --dump-outputs
+DUMP_VIEW_SIZE = (640, 480)
+DUMP_MAX_BLOCKS = 1 << 19
+
+
+def dump_outputs(path, rc, stream, frames_total):
+    """--dump-outputs: what a caller of the loop holds after the last timed frame, as float32 DIR/<name>.npy
+    (under 64 MB in all, whatever the preset):
+      trajectory            [frames, 4, 4]  the loop's current pose of every frame (bf_recon_trajectory)
+      optimized_trajectory  [n, 4, 4]       TrajectoryManager's optimized transforms (bf_recon_optimized_trajectory)
+      blocks                [n, 3]          coordinates of the scene's allocated SDF blocks, sorted (the heap order
+                                            depends on the allocation's atomics); a seeded sample of DUMP_MAX_BLOCKS
+                                            rows of the sorted list when there are more
+      render_depth          [V, H, W]       the scene raycast at 640x480 from V ground-truth poses spread evenly
+      render_normals        [V, H, W, 4]    over the stream, the last frame's among them (the poses are inputs, so
+      render_colors         [V, H, W, 4]    two builds render the same views); pixels without a surface hold 0
+    Every input is seeded and, with --result-lag > 0, the op sequence is repeatable, so two runs with the same
+    arguments write the same arrays up to the order of the float atomics."""
+    import bundlefusion_amd as bfa
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        a = np.ascontiguousarray(a, np.float32)
+        np.save(os.path.join(path, name + ".npy"), np.nan_to_num(a, nan=0.0, posinf=0.0, neginf=0.0))
+
+    rc.synchronize()
+    save("trajectory", rc.trajectory(frames_total))
+    save("optimized_trajectory", rc.optimized_trajectory())
+    blk = rc.export_blocks()
+    blk = blk[blk[:, 3] != 0][:, :3]
+    blk = blk[np.lexsort((blk[:, 2], blk[:, 1], blk[:, 0]))]
+    if len(blk) > DUMP_MAX_BLOCKS:
+        blk = blk[np.sort(np.random.default_rng(0).choice(len(blk), DUMP_MAX_BLOCKS, replace=False))]
+    save("blocks", blk)
+    W, H = DUMP_VIEW_SIZE
+    cam = stream.cam
+    rp = bfa.raycast_params(W, H, fx=cam.fx * W / cam.imageWidth, fy=cam.fy * H / cam.imageHeight)
+    outs = [bfa.DeviceArray((H, W), np.float32)] + [bfa.DeviceArray((H, W, 4), np.float32) for _ in range(3)]
+    views = np.linspace(0, frames_total - 1, DUMP_VIEWS + 1)[1:].round().astype(int)
+    depth, normals, colors = [], [], []
+    for f in views:
+        rc.raycast_device(stream.gt[f], rp, outs)
+        rc.synchronize()
+        depth.append(outs[0].download())
+        normals.append(outs[2].download())
+        colors.append(outs[3].download())
+    save("render_depth", np.stack(depth))
+    save("render_normals", np.stack(normals))
+    save("render_colors", np.stack(colors))
+    log(f"outputs written to {path}")
+
+
 def sens_main(args):
     """FriedLiver over a .sens (BASELINE configs 2 / 3 when copyroom.sens / apt0.sens are present). Multi-GPU
     (torchrun, one app per GPU, every rank on the same .sens and parameters): the TSDF is chunk-sharded over
@@ -463,7 +521,14 @@ def main():
                     help="BFSceneOptions.applyXcdRun: work-list positions per XCD run of the voxel pass (0: the library's 64)")
     ap.add_argument("--apply-rounds", type=int, default=0,
                     help="BFSceneOptions.applyRounds: resident rounds of the voxel pass's grid (0: the library's 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and report everything beside the headline figure: the "
+                         "render window in the fill, the standalone global solve, the end-of-sequence phase, the "
+                         "rooflines, shard balance, raycast, marching cubes and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the loop holds after its last timed step to DIR/<name>.npy "
+                         "(see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-prefix-frames", type=int, default=PREFIX_FRAMES,
                     help="cpu_baseline: frames of the oracle loop prefix (SURVEY.md §8(d): 500)")
     ap.add_argument("--cpu-prefix-budget", type=float, default=PREFIX_BUDGET_S,
@@ -546,7 +611,7 @@ def main():
     # visualizeFrame's render every frame (DepthSensing.cpp:790-793: compactify + CUDARayCastSDF::render after each
     # integration), off the metric per SURVEY 8(d) but part of the reference's frame body: the last frames of the
     # fill (as many as the timed tail, up to 200) run with it, between synchronizations -> frames_per_s_with_render
-    render_frames = min(fill, S * min(args.steps, 20)) if world == 1 else 0
+    render_frames = min(fill, S * min(args.steps, 20)) if world == 1 and args.full else 0
     render_from = fill - render_frames
     # the same number of frames right before it, without the render: the comparison rate for the window
     plain_from = max(0, render_from - render_frames) if render_frames else -1
@@ -568,7 +633,7 @@ def main():
                 t_pw = t_rw - t_pw
             rc.set_render(rp_loop)
         rc.process_frame(f)
-        if (f + 1) % PREFIX_STEP == 0 and f + 1 <= PREFIX_FRAMES:
+        if args.full and (f + 1) % PREFIX_STEP == 0 and f + 1 <= PREFIX_FRAMES:
             # the prefixes the CPU loop baseline may run (untimed region): synchronized checkpoints
             rc.synchronize()
             prefix_times[f + 1] = time.perf_counter() - t_fill
@@ -611,6 +676,60 @@ def main():
         workload += f"; asyncBundling {args.async_bundling}"
     workload += (f"; solved poses applied {args.result_lag} frames after issue" if args.result_lag
                  else "; solved poses applied when polled ready (timing-dependent)")
+    out = {
+        "metric": f"frames/s integrate+global-BA on {args.width}x{args.height} @{args.voxel * 1000:g}mm voxels",
+        "value": frames / dt if cap["errorFlags"] == 0 else None,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if world > 1 else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded analytic room, GPU-rendered depth/colour with the sensor noise model, "
+                "EntryJ stand-in correspondences)",
+        "config": {"workload": workload, "frames": frames_total, "frames_fill": fill, "frames_timed": frames,
+                   "keyframes_final": K,
+                   "parallelism": (f"tsdf-chunk-shard{world}+ba-pair-shard{world}-rccl" if comm is not None
+                                   else f"tsdf-chunk-shard{world}+ba-replicated") if world > 1 else
+                                  (f"rehearsal: rank 0 of tsdf-chunk-shard{args.rehearse_shards}, ba-replicated"
+                                   if args.rehearse_shards > 1 else "single"),
+                   **({"apply_xcd_run": args.apply_xcd_run} if args.apply_xcd_run else {}),
+                   **({"apply_rounds": args.apply_rounds} if args.apply_rounds else {})},
+        "stream": {"frames_per_s_whole_stream": frames_total / (t_fill + dt), "fill_s": t_fill, "timed_s": dt,
+                   "fill_frames_per_s": fill / t_fill if fill else None,
+                   "fill_global_gn_iters": fill_stats["globalGnIterations"],
+                   "note": "whole stream = fill + timed tail, same loop; value is the tail (largest K, largest scene)"},
+        "scene_capacity": {"error_flags": cap["errorFlags"], "peak_candidates": cap["peakCandidates"],
+                           "candidate_capacity": cap["candidateCapacity"],
+                           "candidate_headroom": cap["candidateCapacity"] / max(1, cap["peakCandidates"]),
+                           "heap_free": cap["heapFree"], "num_sdf_blocks": cap["numSDFBlocks"],
+                           "high_water": cap["highWater"],
+                           "note": "peak alloc candidates of one batch over the whole stream vs the candidate "
+                                   "buffer; nonzero error_flags (a dropped block) fail the loop and void value"},
+        "loop": {"ops_per_frame": (st["integrations"] + st["deintegrations"]) / max(1, st["frames"]),
+                 "fix_ops": st["fixOps"], "local_solves": st["localSolves"], "global_solves": st["globalSolves"],
+                 "global_gn_iters": st["globalGnIterations"], "global_pcg_iters": st["globalPcgIterations"],
+                 "removed_pairs": st["removedPairs"], "global_solve_ms": st["globalSolveMs"],
+                 "local_solve_ms": st["localSolveMs"], "integrate_kernel_ms": st["integrateKernelMs"],
+                 "apply_kernel_ms": st["reintegrateKernelMs"],
+                 "host_ms_per_frame": st["hostMs"] / max(1, st["frames"]),
+                 "host_wait_ms_per_frame": st["hostWaitMs"] / max(1, st["frames"]),
+                 "heap_free": rc.heap_free_count(),
+                 "allocated_blocks_scanned_per_compactify": ss["scanned"] / max(1, ss["integrateOps"])},
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rc, stream, frames_total)
+    if not args.full:  # the headline figure and what the timed loop's own counters give for free
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        rc.close()
+        if comm is not None:
+            comm.close()
+        group.close()
+        return
     # dominant kernel: k_apply_ops, the op-batch voxel pass that applies a frame's re-integration
     # fixes (<= 10 x de-integrate + integrate) in one read + write per voxel. Per launch, from the
     # device counters of the same launches:
@@ -687,32 +806,7 @@ def main():
                  "note": "bf_recon_end_sequence(30): 31 past-the-end global solves, the last with sparse weight 1 + "
                          "dense depth 15 (3 x 150 GN x PCG) over every keyframe's 80x60 cache frame, then re-integration "
                          "until the queue drains; untimed, after the timed tail"}
-    out = {
-        "metric": f"frames/s integrate+global-BA on {args.width}x{args.height} @{args.voxel * 1000:g}mm voxels",
-        "value": frames / dt if cap["errorFlags"] == 0 else None,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if world > 1 else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded analytic room, GPU-rendered depth/colour with the sensor noise model, "
-                "EntryJ stand-in correspondences)",
-        "config": {"workload": workload, "frames": frames_total, "frames_fill": fill, "frames_timed": frames,
-                   "keyframes_final": K,
-                   "parallelism": (f"tsdf-chunk-shard{world}+ba-pair-shard{world}-rccl" if comm is not None
-                                   else f"tsdf-chunk-shard{world}+ba-replicated") if world > 1 else
-                                  (f"rehearsal: rank 0 of tsdf-chunk-shard{args.rehearse_shards}, ba-replicated"
-                                   if args.rehearse_shards > 1 else "single"),
-                   **({"apply_xcd_run": args.apply_xcd_run} if args.apply_xcd_run else {}),
-                   **({"apply_rounds": args.apply_rounds} if args.apply_rounds else {})},
-        "stream": {"frames_per_s_whole_stream": frames_total / (t_fill + dt), "fill_s": t_fill, "timed_s": dt,
-                   "fill_frames_per_s": fill / t_fill if fill else None,
-                   "fill_global_gn_iters": fill_stats["globalGnIterations"],
-                   "note": "whole stream = fill + timed tail, same loop; value is the tail (largest K, largest scene)"},
+    out.update({
         "frames_per_s_with_render": (render_frames / t_rw) if t_rw else None,
         "render_in_loop": {"frames": render_frames, "frames_window": [render_from, fill], "s": t_rw,
                            "frames_per_s_window_before_without_render": ((render_from - plain_from) / t_pw) if t_pw else None,
@@ -723,13 +817,6 @@ def main():
                                    "frames_per_s_window_before_without_render (the as many frames right before it, "
                                    "no render), not with value (the timed tail: larger K and scene); the reference "
                                    "renders every frame for display, which SURVEY 8(d) keeps out of the metric"} if render_frames else None,
-        "scene_capacity": {"error_flags": cap["errorFlags"], "peak_candidates": cap["peakCandidates"],
-                           "candidate_capacity": cap["candidateCapacity"],
-                           "candidate_headroom": cap["candidateCapacity"] / max(1, cap["peakCandidates"]),
-                           "heap_free": cap["heapFree"], "num_sdf_blocks": cap["numSDFBlocks"],
-                           "high_water": cap["highWater"],
-                           "note": "peak alloc candidates of one batch over the whole stream vs the candidate "
-                                   "buffer; nonzero error_flags (a dropped block) fail the loop and void value"},
         "ms_per_gn_iter": solo["ms_per_gn_iter"],
         "global_solve": dict(solo, ms_per_gn_iter_in_loop=ms_gn_loop,
                              pcg_kernel_us_per_iter_in_loop=(st["globalPcgKernelMs"] * 1e3 / max(1, st["globalPcgIterations"])
@@ -768,17 +855,8 @@ def main():
                      "valu": valu,
                      "k_integrate": {"launches": st["integrateLaunches"],
                                      "avg_us": st["integrateKernelMs"] * 1e3 / max(1, st["integrateLaunches"])}},
-        "loop": {"ops_per_frame": (st["integrations"] + st["deintegrations"]) / max(1, st["frames"]),
-                 "fix_ops": st["fixOps"], "local_solves": st["localSolves"], "global_solves": st["globalSolves"],
-                 "global_gn_iters": st["globalGnIterations"], "global_pcg_iters": st["globalPcgIterations"],
-                 "removed_pairs": st["removedPairs"], "global_solve_ms": st["globalSolveMs"],
-                 "local_solve_ms": st["localSolveMs"], "integrate_kernel_ms": st["integrateKernelMs"],
-                 "apply_kernel_ms": st["reintegrateKernelMs"],
-                 "host_ms_per_frame": st["hostMs"] / max(1, st["frames"]),
-                 "host_wait_ms_per_frame": st["hostWaitMs"] / max(1, st["frames"]),
-                 "heap_free": rc.heap_free_count(),
-                 "allocated_blocks_scanned_per_compactify": ss["scanned"] / max(1, ss["integrateOps"])},
-    }
+    })
+    out["loop"]["heap_free"] = rc.heap_free_count()  # after the end phase
     # multi-GPU TSDF sharding: how evenly 1 m chunk ownership spreads the final
     # scene's blocks and the timed frames' in-frustum blocks over G = 2 / 4 / 8 ranks (host mirror)
     if world == 1:

@@ -1,9 +1,9 @@
 """Writes tests/golden/zparameters_reference.json: every `key = value;` of the reference's own parameter files
 (FriedLiver/zParametersDefault.txt, FriedLiver/zParametersBundlingDefault.txt), read here with an independent
 parser of mLib's ParameterFile format (one `name = value;` per line, `//` comments). The JSON holds the raw value
-text per key, in file order: the data the two files give the boundary, so tests off this container (where
-/root/reference does not exist) can rebuild parameter files with exactly these settings.
-Usage: python tests/golden/make_zparameters_fixture.py [/root/reference]"""
+text per key, in file order: the data the two files give the boundary, so tests can rebuild parameter files with
+exactly these settings. Verbatim copies of the two files are kept under tests/golden/FriedLiver/.
+Usage: python tests/golden/make_zparameters_fixture.py [directory that holds FriedLiver/]"""
 import json
 import os
 import sys
@@ -25,7 +25,7 @@ def read_parameter_text(text: str) -> dict:
     return out
 
 
-def main(ref="/root/reference"):
+def main(ref=HERE):
     data = {"source": "kanster/BundleFusion FriedLiver/zParameters*.txt, parsed by tests/golden/make_zparameters_fixture.py"}
     for f in FILES:
         with open(os.path.join(ref, "FriedLiver", f), encoding="latin-1") as fh:

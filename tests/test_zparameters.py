@@ -3,8 +3,8 @@
 holds). GlobalAppState / GlobalBundlingState read them with mLib's ParameterFile (GlobalAppState.h:128-136,
 GlobalBundlingState.h:15-65, FriedLiver.cpp:228-250).
 
-* the committed fixture (tests/golden/zparameters_reference.json) equals the files, read independently
-  (container only: /root/reference does not exist on the GPU box);
+* the committed fixture (tests/golden/zparameters_reference.json) equals the files (verbatim copies under
+  tests/golden/FriedLiver/), read independently;
 * the C++ parameter path (bf_params_*) reads the files verbatim to the same values, key by key;
 * params.py's APP_DEFAULTS / BUNDLING_DEFAULTS equal the files, except the documented s_sensorIdx 7 -> 8
   (SensorDataReader, the offline .sens reader the path runs; the file's 7 is the StructureSensor);
@@ -22,9 +22,7 @@ from bundlefusion_amd.io import ParameterFile
 from bundlefusion_amd.params import APP_DEFAULTS, BUNDLING_DEFAULTS, write_parameter_files
 from golden.make_zparameters_fixture import FILES, read_parameter_text
 
-REF = "/root/reference/FriedLiver"
-HAVE_REF = all(os.path.exists(os.path.join(REF, f)) for f in FILES)
-needs_ref = pytest.mark.skipif(not HAVE_REF, reason="the reference tree exists only in the build container")
+REF = os.path.join(os.path.dirname(__file__), "golden", "FriedLiver")  # verbatim copies of the two files
 FIXTURE = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "zparameters_reference.json")))
 APP_FILE, BUNDLING_FILE = FILES
 DEVIATIONS = {"s_sensorIdx": (7, 8)}  # app file: StructureSensor in the file, SensorDataReader on this path
@@ -46,14 +44,12 @@ def same(a, b) -> bool:
     return np.array_equal(np.float32(a), np.float32(b))
 
 
-@needs_ref
 def test_fixture_equals_reference_files():
     for f in FILES:
         with open(os.path.join(REF, f), encoding="latin-1") as fh:
             assert read_parameter_text(fh.read()) == FIXTURE[f], f
 
 
-@needs_ref
 @pytest.mark.parametrize("name", FILES)
 def test_cpp_parser_reads_reference_files_verbatim(name):
     pf = ParameterFile(os.path.join(REF, name))
@@ -124,7 +120,6 @@ def _resolved(app, bundling, sens):
     return _fields(info), _fields(loop)
 
 
-@needs_ref
 def test_app_accepts_reference_files_with_only_the_sensor_override(sens):
     info, loop = _resolved(os.path.join(REF, APP_FILE), os.path.join(REF, BUNDLING_FILE), sens)
     A = {k: typed(v) for k, v in FIXTURE[APP_FILE].items()}
@@ -175,7 +170,6 @@ def test_app_accepts_reference_files_with_only_the_sensor_override(sens):
     assert loop["solver.denseOverlapSubsample"] == B["s_denseOverlapCheckSubsampleFactor"]
 
 
-@needs_ref
 def test_fixture_files_resolve_like_the_reference_files(sens, tmp_path):
     got = _resolved(*_write_fixture_files(str(tmp_path)), sens)
     ref = _resolved(os.path.join(REF, APP_FILE), os.path.join(REF, BUNDLING_FILE), sens)

@@ -9,7 +9,7 @@ TAG=$1; GS=$2; shift 2
 OUT=gpurun_out/${TAG}
 mkdir -p $OUT
 for G in $GS; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/g$G -o run --output-format csv -- python3 bench.py --no-cpu-baseline --rehearse-shards $G "$@" > $OUT/bench_g$G.json 2> $OUT/bench_g$G.err || { echo "G=$G failed"; tail -20 $OUT/bench_g$G.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/g$G -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --rehearse-shards $G "$@" > $OUT/bench_g$G.json 2> $OUT/bench_g$G.err || { echo "G=$G failed"; tail -20 $OUT/bench_g$G.err; exit 1; }
   python3 tools/prof_summary.py $OUT/g$G/run_kernel_stats.csv > $OUT/kernel_stats_g$G.txt
   rm -f $OUT/g$G/run_kernel_trace.csv
   echo "G=$G: $(python3 -c "import json; d=json.loads(open('$OUT/bench_g$G.json').read().strip().splitlines()[-1]); print('%.1f frames/s' % d['value'], d['config']['parallelism'])")"
