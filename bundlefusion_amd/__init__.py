@@ -17,7 +17,8 @@ from .abi import (BFDepthCameraParams, BFHashParams, BFMarchingCubesParams, BFRa
                   BFSynthScene, BFTsdfStats, HASH_ENTRY_DTYPE, VOXEL_DTYPE)
 
 __all__ = ["lib", "BFError", "DeviceArray", "SceneRepHashSDF", "hash_params", "depth_camera",
-           "synth_scene", "synth_pose", "synth_render", "synth_render_host", "mc_params", "mesh_merge", "mesh_save_ply"]
+           "synth_scene", "synth_pose", "synth_render", "synth_render_host", "mc_params", "mesh_merge", "mesh_save_ply",
+           "Matcher", "matcher_options"]
 
 _lib = None
 
@@ -373,3 +374,10 @@ def synth_render_host(scene: BFSynthScene, T, cam: BFDepthCameraParams, noise_se
     check(lib().bf_synth_render_host(C.byref(scene), abi.mat(T), C.byref(cam), C.c_uint32(noise_seed),
                                      C.c_uint32(frame), abi.f32p(d), abi.u8p(c)))
     return d, c
+
+
+def __getattr__(name):  # the matcher binding imports this module's helpers, so it is resolved on first use
+    if name in ("Matcher", "matcher_options"):
+        from . import match
+        return getattr(match, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

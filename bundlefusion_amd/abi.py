@@ -219,6 +219,21 @@ class BFCorrOptions(C.Structure):  # include/bf/types.h
                 ("minPerPair", C.c_uint32)]
 
 
+class BFSiftKeyPoint(C.Structure):  # include/bf/types.h, SIFTKeyPoint
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("scale", C.c_float), ("depth", C.c_float)]
+
+
+class BFMatcherOptions(C.Structure):  # include/bf/types.h: the sparse matcher (bf_matcher_*)
+    _fields_ = [("maxImages", C.c_uint32), ("maxKeysPerImage", C.c_uint32), ("matchThresh", C.c_float),
+                ("ratioMax", C.c_float), ("minNumMatches", C.c_uint32), ("maxKabschRes2", C.c_float),
+                ("intrinsicsInv", C.c_float * 16), ("reserved", C.c_uint32 * 2)]
+
+
+SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
+MAX_MATCHES_RAW, MAX_MATCHES_FILTERED, MATCH_MAX_KEYS_PER_IMAGE = 128, 25, 1024
+assert C.sizeof(BFSiftKeyPoint) == 16 and SIFT_KEYPOINT_DTYPE.itemsize == 16
+
+
 class BFVoxelOp(C.Structure):  # include/bf/bf.h
     _fields_ = [("T", C.c_float * 16), ("depth", C.c_void_p), ("color", C.c_void_p), ("deintegrate", C.c_uint32),
                 ("reserved", C.c_uint32)]

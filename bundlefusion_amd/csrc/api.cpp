@@ -14,6 +14,7 @@
 #include "frames.h"
 #include "app.h"
 #include "frontend.h"
+#include "match.h"
 
 #include <cstring>
 #include <memory>
@@ -138,6 +139,10 @@ struct bf_preproc {
     hipStream_t stream = nullptr;
     Preproc* p = nullptr;
 };
+struct bf_matcher {
+    hipStream_t stream = nullptr;
+    Matcher* m = nullptr;
+};
 
 extern "C" {
 
@@ -164,6 +169,8 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFMarchingCubesParams", sizeof(BFMarchingCubesParams)},
         {"BFCacheOptions", sizeof(BFCacheOptions)},
         {"BFCorrOptions", sizeof(BFCorrOptions)},
+        {"BFSiftKeyPoint", sizeof(BFSiftKeyPoint)},
+        {"BFMatcherOptions", sizeof(BFMatcherOptions)},
         {"BFCachedFrame", sizeof(BFCachedFrame)},
         {"BFSceneOptions", sizeof(BFSceneOptions)},
         {"BFVoxelOp", sizeof(BFVoxelOp)},
@@ -1190,6 +1197,146 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
     BF_TRY
     BF_REQUIRE(o && n, BF_ERR_ARG, "null argument");
     *n = corr_from_depth(depth, transforms, transformsInv, curFrame, startFrame, *o, out, cap, total);
+    BF_CATCH
+}
+
+// ---- sparse matcher (SIFTImageManager + SiftMatchCU + Bundler::matchAndFilter) -------------------
+int bf_matcher_create(const BFMatcherOptions* opts, bf_matcher** out) {
+    BF_TRY
+    BF_REQUIRE(opts && out, BF_ERR_ARG, "null argument");
+    *out = nullptr;
+    const MatcherConfig cfg = make_matcher_config(opts);  // option checks before any device work
+    bf_matcher* h = new bf_matcher();
+    try {
+        BF_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        h->m = new Matcher(cfg, h->stream);
+    } catch (...) {
+        if (h->stream) (void)hipStreamDestroy(h->stream);
+        delete h;
+        throw;
+    }
+    *out = h;
+    BF_CATCH
+}
+int bf_matcher_destroy(bf_matcher* m) {
+    BF_TRY
+    if (m) {
+        if (m->stream) (void)hipStreamSynchronize(m->stream);
+        delete m->m;
+        if (m->stream) (void)hipStreamDestroy(m->stream);
+        delete m;
+    }
+    BF_CATCH
+}
+int bf_matcher_reset(bf_matcher* m) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->reset();
+    BF_CATCH
+}
+int bf_matcher_add_image(bf_matcher* m, const BFSiftKeyPoint* keys, const uint8_t* descs, uint32_t n, uint32_t* index) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    const uint32_t i = m->m->addImage(keys, descs, n);
+    if (index) *index = i;
+    BF_CATCH
+}
+int bf_matcher_num_images(bf_matcher* m, uint32_t* n) {
+    BF_TRY
+    BF_REQUIRE(m && n, BF_ERR_ARG, "null argument");
+    *n = m->m->numImages();
+    BF_CATCH
+}
+int bf_matcher_num_keys(bf_matcher* m, uint32_t image, uint32_t* n, uint32_t* offset) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    BF_REQUIRE(image < m->m->numImages(), BF_ERR_ARG, "image >= numImages");
+    if (n) *n = m->m->numKeys(image);
+    if (offset) *offset = m->m->keyOffset(image);
+    BF_CATCH
+}
+int bf_matcher_set_valid(bf_matcher* m, uint32_t image, int valid) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    BF_REQUIRE(image < m->m->numImages(), BF_ERR_ARG, "image >= numImages");
+    m->m->setValid(image, valid);
+    BF_CATCH
+}
+int bf_matcher_get_valid(bf_matcher* m, uint32_t image, int* valid) {
+    BF_TRY
+    BF_REQUIRE(m && valid, BF_ERR_ARG, "null argument");
+    BF_REQUIRE(image < m->m->numImages(), BF_ERR_ARG, "image >= numImages");
+    *valid = m->m->valid(image);
+    BF_CATCH
+}
+int bf_matcher_match(bf_matcher* m, uint32_t curFrame, uint32_t startFrame) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->match(curFrame, startFrame);
+    BF_CATCH
+}
+int bf_matcher_filter(bf_matcher* m, uint32_t curFrame, uint32_t startFrame) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->filter(curFrame, startFrame);
+    BF_CATCH
+}
+int bf_matcher_filter_frames(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, uint32_t* lastMatchedFrame) {
+    BF_TRY
+    BF_REQUIRE(m && lastMatchedFrame, BF_ERR_ARG, "null argument");
+    *lastMatchedFrame = m->m->filterFrames(curFrame, startFrame);
+    BF_CATCH
+}
+int bf_matcher_add_to_residuals(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, BFEntryJ* out, uint32_t* keyIdx,
+                                uint32_t cap, uint32_t* n, uint32_t* total) {
+    BF_TRY
+    BF_REQUIRE(m && n, BF_ERR_ARG, "null argument");
+    *n = m->m->addToResiduals(curFrame, startFrame, out, keyIdx, cap, total);
+    BF_CATCH
+}
+int bf_matcher_raw_matches(bf_matcher* m, uint32_t prev, uint32_t* count, uint32_t* idx, float* dist) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->rawMatches(prev, count, idx, dist);
+    BF_CATCH
+}
+int bf_matcher_filtered_matches(bf_matcher* m, uint32_t prev, uint32_t* count, uint32_t* idx, float* dist) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->filteredMatches(prev, count, idx, dist);
+    BF_CATCH
+}
+int bf_matcher_transforms(bf_matcher* m, uint32_t prev, float T[16], float Tinv[16]) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->transforms(prev, T, Tinv);
+    BF_CATCH
+}
+int bf_matcher_debug_dots(bf_matcher* m, uint32_t prev, uint32_t curFrame, const uint32_t* rows, uint32_t nRows,
+                          const uint32_t* cols, uint32_t nCols, int32_t* dots, int32_t* rowStats) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->debugDots(prev, curFrame, rows, nRows, cols, nCols, dots, rowStats);
+    BF_CATCH
+}
+int bf_matcher_synchronize(bf_matcher* m) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    BF_HIP(hipStreamSynchronize(m->stream));
+    BF_CATCH
+}
+int bf_matcher_timer_start(bf_matcher* m, bf_timer* t) {
+    BF_TRY
+    BF_REQUIRE(m && t, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->a, m->stream));
+    BF_CATCH
+}
+int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms) {
+    BF_TRY
+    BF_REQUIRE(m && t && ms, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->b, m->stream));
+    BF_HIP(hipEventSynchronize(t->b));
+    BF_HIP(hipEventElapsedTime(ms, t->a, t->b));
     BF_CATCH
 }
 

@@ -1,0 +1,77 @@
+// match.h — the sparse matcher (match.hip): image store of key points + descriptors, descriptor matching on
+// the int8 matrix cores, the Kabsch key-point match filter, filterFrames and the EntryJ producer. One handle
+// per Bundler (local / global), everything queued on the handle's stream, no device allocation after the ctor.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/bf/bf.h"
+#include "bf_runtime.h"
+
+namespace bf {
+
+struct MatcherConfig {
+    uint32_t maxImages = 0, maxKeys = 0;
+    float matchThresh = 0.7f, ratioMax = 0.8f;
+    uint32_t minNumMatches = 5;
+    float maxKabschRes2 = 0.0004f;
+    float kinv[16] = {};
+};
+
+// BFMatcherOptions -> config with the defaults filled in; throws BF_ERR_ARG on invalid options (host only)
+MatcherConfig make_matcher_config(const BFMatcherOptions* o);
+
+class Matcher {
+public:
+    static constexpr uint32_t kRaw = BF_MAX_MATCHES_RAW, kFilt = BF_MAX_MATCHES_FILTERED, kDbg = 32;
+
+    Matcher(const MatcherConfig& cfg, hipStream_t stream);
+    ~Matcher();
+    void reset();
+    uint32_t addImage(const BFSiftKeyPoint* keys, const uint8_t* descs, uint32_t n);
+    uint32_t numImages() const { return (uint32_t)num_.size(); }
+    uint32_t numKeys(uint32_t i) const { return num_[i]; }
+    uint32_t keyOffset(uint32_t i) const { return off_[i]; }
+    void setValid(uint32_t i, int v);
+    int valid(uint32_t i) const { return valid_[i]; }
+    const MatcherConfig& config() const { return cfg_; }
+
+    void match(uint32_t cur, uint32_t start);
+    void filter(uint32_t cur, uint32_t start);
+    uint32_t filterFrames(uint32_t cur, uint32_t start);
+    uint32_t addToResiduals(uint32_t cur, uint32_t start, BFEntryJ* out, uint32_t* keyIdx, uint32_t cap, uint32_t* total);
+    void rawMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist);
+    void filteredMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist);
+    void transforms(uint32_t prev, float* T, float* Tinv);
+    void debugDots(uint32_t prev, uint32_t cur, const uint32_t* rows, uint32_t nRows, const uint32_t* cols, uint32_t nCols,
+                   int32_t* dots, int32_t* rowStats);
+
+private:
+    void uploadTable();
+    void launchMatch(uint32_t cur, uint32_t start, uint32_t pairs, bool debug, uint32_t nRows, uint32_t nCols);
+
+    MatcherConfig cfg_;
+    hipStream_t stream_;
+    std::vector<uint32_t> num_, off_;
+    std::vector<int> valid_;
+    uint32_t totalKeys_ = 0;
+    bool tableDirty_ = true;
+    DevBuf<BFSiftKeyPoint> keys_;  // [maxImages * maxKeys], linear
+    DevBuf<uint8_t> descs_;        // [maxImages * maxKeys][128]
+    DevBuf<int32_t> sums_;         // byte sum per descriptor
+    DevBuf<uint32_t> table_;       // per image {offset, count, valid, 0}
+    DevBuf<uint32_t> rawCount_, filtCount_;  // [maxImages]
+    DevBuf<uint2> rawIdx_, filtIdx_;         // [maxImages][128] / [maxImages][25]
+    DevBuf<float> rawDist_, filtDist_;
+    DevBuf<float> T_, Tinv_;                 // [maxImages][16]
+    DevBuf<uint32_t> base_;                  // [maxImages] EntryJ base per pair
+    DevBuf<uint32_t> dbgSel_;                // rows[32], cols[32]
+    DevBuf<int32_t> dbgOut_;                 // dots[32 * 32], rowStats[3 * 32]
+    uint32_t* hostTable_ = nullptr;          // pinned, 4 * maxImages
+    uint32_t* hostCounts_ = nullptr;         // pinned, maxImages
+    uint32_t* hostBase_ = nullptr;           // pinned, maxImages
+};
+
+}  // namespace bf

@@ -1,0 +1,913 @@
+// match.hip — the sparse matcher: descriptor matching + Kabsch filter to EntryJ. Restates the matching side of
+// SIFTImageManager + SiftMatchCU + Bundler::matchAndFilter (paths relative to FriedLiver/Source/):
+//   Bundler.cpp:103-249, SiftGPU/ProgramCU.cu:1634-1936 (MultiplyDescriptor / RowMatch / ColMatch),
+//   SiftGPU/SIFTImageManager.cu:59-314, 610-687, SiftGPU/SIFTImageManager.cpp:44-83, 551-575,
+//   SiftGPU/cuda_kabsch.h:73-229, 281-502.
+// The DoG detector / descriptor, the surface-area and dense-verify filters, tryRevalidation and fuseToGlobal are
+// not here.
+//
+// k_match — one workgroup (4 waves) per image pair (prev, cur), every pair of a call in one launch. The reference
+// writes the num1 x num2 int32 dot matrix to memory and reduces it with two more kernels per pair; here it never
+// leaves the registers:
+//   * dot[a][b] = sum_k prev[a][k] * cur[b][k] on v_mfma_i32_32x32x32_i8. The instruction is signed and the
+//     descriptors are unsigned bytes, so it is fed d - 128 (d ^ 0x80) and the exact unsigned dot is restored with
+//     sum ab = sum (a-128)(b-128) + 128 (sum a + sum b) - 128 * 16384 from per-descriptor byte sums (all int32).
+//     Both operands of a k-step are 16 contiguous bytes of a descriptor at the same offset, so the k order inside
+//     the instruction cancels; the row / column maps are A: row = lane & 31, B: col = lane & 31,
+//     D: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+//   * cur's descriptors sit in LDS in chunks of 512 columns (64 KB, 16-byte units XOR-swizzled by column); a wave
+//     owns the 32-row strips w, w + 4, ... of prev (A fragments in 16 VGPRs from global memory) and walks the
+//     chunk's column tiles.
+//   * best / second best / argument per ROW: per lane over its column of every tile, then a butterfly over the 32
+//     lanes of a strip half, merged into an LDS row table (a strip's rows belong to one wave). Per COLUMN: per
+//     lane over its 16 rows into a per-wave, per-lane-half LDS table, merged over the 8 tables after each chunk.
+//     Ties go to the lowest index and the second best then equals the best (RowMatch_Kernel's strict >).
+//   * acceptance, mutual check, and the raw list ordered by (dot descending, cur key ascending), first 128 kept:
+//     the one deliberate departure from the reference, which appends in race order (atomicAdd) before its sort
+//     and keeps an arbitrary 128 of more; the count written is the true number of mutual matches.
+// k_filter — one wave per pair, lane 0 runs filterKeyPointMatches' greedy loop (the reference runs it on one
+// thread too); Kabsch's 3x3 SVD and the covariance eigenvalues use a double-precision Jacobi iteration.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "../../include/bf/bf.h"
+#include "bf_runtime.h"
+#include "match.h"
+
+namespace bf {
+
+namespace {
+
+constexpr int MATCH_WG = 256;
+constexpr uint32_t MAXK = BF_MATCH_MAX_KEYS_PER_IMAGE;  // rows / columns of one pair
+constexpr uint32_t CHUNK = 512;                         // columns of cur resident in LDS
+constexpr uint32_t RAW = BF_MAX_MATCHES_RAW, FILT = BF_MAX_MATCHES_FILTERED;
+constexpr uint32_t DBG_MAX = Matcher::kDbg;
+// LDS (ints): descriptors, per-wave column tables, column table, row table, scratch
+constexpr uint32_t LDS_DESC = CHUNK * 32, LDS_COLW = 3 * 4 * 2 * CHUNK, LDS_COL = 3 * MAXK, LDS_ROW = 3 * MAXK, LDS_MISC = 8;
+constexpr size_t MATCH_LDS_BYTES = 4 * (size_t)(LDS_DESC + LDS_COLW + LDS_COL + LDS_ROW + LDS_MISC);
+static_assert(MATCH_LDS_BYTES <= 160 * 1024, "k_match's LDS exceeds a gfx950 workgroup's 160 KB");
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+struct MatchArgs {
+    const uint8_t* descs;
+    const int32_t* sums;
+    const uint32_t* table;  // per image {offset, count, valid, 0}
+    uint32_t cur, start;
+    float thresh, ratio;
+    uint32_t* rawCount;
+    uint2* rawIdx;
+    float* rawDist;
+    const uint32_t* dbgSel;  // rows[32], cols[32]
+    int32_t* dbgOut;         // dots[32 * 32], rowStats[3 * 32]
+    uint32_t dbgRows, dbgCols;
+};
+
+// (best, next, arg) <- merged with (b2, n2, a2): ties on best go to the lower index, next = best then
+__device__ __forceinline__ void merge3(int& b, int& n, int& a, int b2, int n2, int a2) {
+    const bool second = b2 > b || (b2 == b && (uint32_t)a2 < (uint32_t)a);
+    const int lo = min(b, b2);
+    n = max(lo, max(n, n2));
+    b = max(b, b2);
+    a = second ? a2 : a;
+}
+
+__device__ __forceinline__ float match_dist(int dot) {
+    return acosf(fminf((float)dot * 0.000003814697265625f, 1.0f));  // 2^-18 (RowMatch_Kernel, ProgramCU.cu:1824)
+}
+
+__device__ __forceinline__ v4i flip128(int4 v) {
+    v4i r;
+    r.x = v.x ^ (int)0x80808080;
+    r.y = v.y ^ (int)0x80808080;
+    r.z = v.z ^ (int)0x80808080;
+    r.w = v.w ^ (int)0x80808080;
+    return r;
+}
+
+template <bool DBG>
+__global__ __launch_bounds__(MATCH_WG) void k_match(MatchArgs A) {
+    extern __shared__ int4 smem4[];
+    v4i* sDesc = (v4i*)smem4;
+    int* sColW = (int*)smem4 + LDS_DESC;
+    int* sCol = sColW + LDS_COLW;
+    int* sRow = sCol + LDS_COL;
+    int* sMisc = sRow + LDS_ROW;
+
+    const uint32_t prev = A.start + blockIdx.x;
+    if (prev == A.cur) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t l31 = lane & 31, h = lane >> 5;
+    const uint32_t prevOff = A.table[4 * prev], nPrev = A.table[4 * prev + 1], prevValid = A.table[4 * prev + 2];
+    const uint32_t curOff = A.table[4 * A.cur], nCur = A.table[4 * A.cur + 1];
+    uint2* oIdx = A.rawIdx + (size_t)prev * RAW;
+    float* oDist = A.rawDist + (size_t)prev * RAW;
+    if (!prevValid || nPrev == 0 || nCur == 0 || nPrev > MAXK || nCur > MAXK) {  // workgroup-uniform
+        if (tid < RAW) {
+            oIdx[tid] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+            oDist[tid] = 999.0f;
+        }
+        if (tid == 0) A.rawCount[prev] = 0;
+        return;
+    }
+
+    for (uint32_t k = tid; k < MAXK; k += MATCH_WG) {
+        sRow[k] = 0;
+        sRow[MAXK + k] = 0;
+        sRow[2 * MAXK + k] = -1;
+    }
+    const uint32_t nRowTiles = (nPrev + 31) / 32;
+    const int4* gPrev = (const int4*)A.descs + (size_t)prevOff * 8;
+    const int4* gCur = (const int4*)A.descs + (size_t)curOff * 8;
+    const int32_t* sumPrev = A.sums + prevOff;
+    const int32_t* sumCur = A.sums + curOff;
+
+    for (uint32_t c0 = 0; c0 < nCur; c0 += CHUNK) {
+        const uint32_t chunkCols = min(CHUNK, ((nCur - c0) + 31u) & ~31u);
+        const uint32_t nColTiles = chunkCols / 32;
+        __syncthreads();  // the previous chunk's tables are merged, its descriptors no longer read
+        for (uint32_t u = tid; u < chunkCols * 8; u += MATCH_WG) {
+            const uint32_t cl = u >> 3, p = u & 7, col = c0 + cl;
+            v4i v = {0, 0, 0, 0};
+            if (col < nCur) v = flip128(gCur[(size_t)col * 8 + p]);
+            sDesc[cl * 8 + (p ^ (cl & 7))] = v;
+        }
+        for (uint32_t k = lane; k < 2 * CHUNK; k += 64) {  // this wave's two column tables
+            sColW[(0 * 4 + wave) * 2 * CHUNK + k] = 0;
+            sColW[(1 * 4 + wave) * 2 * CHUNK + k] = 0;
+            sColW[(2 * 4 + wave) * 2 * CHUNK + k] = -1;
+        }
+        __syncthreads();
+
+        for (uint32_t rs = wave; rs < nRowTiles; rs += 4) {
+            // A fragments: row rs * 32 + (lane & 31), bytes [32 s + 16 h, + 16) of k-step s
+            const uint32_t arow = rs * 32 + l31;
+            v4i a[4];
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                a[s] = v4i{0, 0, 0, 0};
+                if (arow < nPrev) a[s] = flip128(gPrev[(size_t)arow * 8 + 2 * s + h]);
+            }
+            // this lane's 16 rows of the accumulator tile
+            int rterm[16], rb[16], rn[16], ra[16];
+            uint32_t rmask = 0;
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const uint32_t row = rs * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const bool ok = row < nPrev;
+                rterm[i] = ok ? 128 * sumPrev[row] : 0;
+                rmask |= ok ? (1u << i) : 0u;
+                rb[i] = 0;
+                rn[i] = 0;
+                ra[i] = -1;
+            }
+            for (uint32_t ct = 0; ct < nColTiles; ct++) {
+                const uint32_t cl = ct * 32 + l31, col = c0 + cl;
+                v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    const v4i b = sDesc[cl * 8 + ((2 * s + h) ^ (cl & 7))];
+                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], b, acc, 0, 0, 0);
+                }
+                const bool colOk = col < nCur;
+                const int cterm = colOk ? 128 * sumCur[col] - 128 * 16384 : 0;
+                const uint32_t ci = (wave * 2 + h) * CHUNK + cl;
+                int cb = sColW[ci], cn = sColW[4 * 2 * CHUNK + ci], ca = sColW[2 * 4 * 2 * CHUNK + ci];
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    const int row = (int)(rs * 32 + (i & 3) + 8 * (i >> 2) + 4 * h);
+                    int v = acc[i] + rterm[i] + cterm;
+                    v = (colOk && ((rmask >> i) & 1u)) ? v : 0;  // a padded row / column never beats the initial 0
+                    if constexpr (DBG) {
+                        for (uint32_t r = 0; r < A.dbgRows; r++)
+                            for (uint32_t c = 0; c < A.dbgCols; c++)
+                                if (A.dbgSel[r] == (uint32_t)row && A.dbgSel[DBG_MAX + c] == col) A.dbgOut[r * A.dbgCols + c] = v;
+                    }
+                    // row statistics (columns arrive in ascending order: strict > keeps the lowest index)
+                    const bool tr = v > rb[i];
+                    rn[i] = tr ? rb[i] : max(rn[i], v);
+                    ra[i] = tr ? (int)col : ra[i];
+                    rb[i] = tr ? v : rb[i];
+                    // column statistics (rows arrive in ascending order)
+                    const bool tc = v > cb;
+                    cn = tc ? cb : max(cn, v);
+                    ca = tc ? row : ca;
+                    cb = tc ? v : cb;
+                }
+                sColW[ci] = cb;
+                sColW[4 * 2 * CHUNK + ci] = cn;
+                sColW[2 * 4 * 2 * CHUNK + ci] = ca;
+            }
+            // rows: butterfly over the 32 lanes (columns) of this half, then into the row table
+#pragma unroll
+            for (int step = 1; step < 32; step <<= 1) {
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    const int b2 = __shfl_xor(rb[i], step), n2 = __shfl_xor(rn[i], step), a2 = __shfl_xor(ra[i], step);
+                    merge3(rb[i], rn[i], ra[i], b2, n2, a2);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                if (l31 == (uint32_t)i) {
+                    const uint32_t row = rs * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;  // < MAXK
+                    int b = sRow[row], n = sRow[MAXK + row], ar = sRow[2 * MAXK + row];  // earlier chunks: lower columns
+                    merge3(b, n, ar, rb[i], rn[i], ra[i]);
+                    sRow[row] = b;
+                    sRow[MAXK + row] = n;
+                    sRow[2 * MAXK + row] = ar;
+                }
+            }
+        }
+        __syncthreads();
+        // columns of this chunk: merge the 4 waves x 2 halves
+        for (uint32_t cl = tid; cl < chunkCols; cl += MATCH_WG) {
+            int b = 0, n = 0, ar = -1;
+            for (uint32_t t = 0; t < 8; t++) {
+                const uint32_t ci = t * CHUNK + cl;
+                merge3(b, n, ar, sColW[ci], sColW[4 * 2 * CHUNK + ci], sColW[2 * 4 * 2 * CHUNK + ci]);
+            }
+            sCol[c0 + cl] = b;
+            sCol[MAXK + c0 + cl] = n;
+            sCol[2 * MAXK + c0 + cl] = ar;
+        }
+    }
+    __syncthreads();
+
+    if constexpr (DBG) {
+        if (tid < A.dbgRows) {
+            const uint32_t row = A.dbgSel[tid];
+            for (int k = 0; k < 3; k++) A.dbgOut[DBG_MAX * DBG_MAX + 3 * tid + k] = row < MAXK ? sRow[k * MAXK + row] : 0;
+        }
+    }
+
+    // acceptance per row (GetRowMatch): result index or -1, and the row's distance
+    int* rowRes = sColW;                        // [MAXK]
+    float* rowDist = (float*)(sColW + MAXK);    // [MAXK]
+    for (uint32_t r = tid; r < nPrev; r += MATCH_WG) {
+        const float dist = match_dist(sRow[r]), distn = match_dist(sRow[MAXK + r]);
+        rowRes[r] = (dist < A.thresh && dist < distn * A.ratio) ? sRow[2 * MAXK + r] : -1;
+        rowDist[r] = dist;
+    }
+    __syncthreads();
+
+    // mutual matches in column order (GetColMatch): thread t owns columns 4 t .. 4 t + 3
+    int* mDot = (int*)sDesc;                 // [MAXK]
+    int* mA = mDot + MAXK;
+    int* mB = mA + MAXK;
+    float* mDist = (float*)(mB + MAXK);
+    int fa[4];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t b = 4 * tid + j;
+        fa[j] = -1;
+        if (b < nCur) {
+            const float dist = match_dist(sCol[b]), distn = match_dist(sCol[MAXK + b]);
+            const int f1 = (dist < A.thresh && dist < distn * A.ratio) ? sCol[2 * MAXK + b] : -1;
+            if (f1 >= 0 && rowRes[f1] == (int)b) {
+                fa[j] = f1;
+                mine++;
+            }
+        }
+    }
+    uint32_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= (uint32_t)o) incl += t;
+    }
+    if (lane == 63) sMisc[wave] = (int)incl;
+    __syncthreads();
+    uint32_t at = incl - mine, total = 0;
+    for (uint32_t w = 0; w < 4; w++) {
+        at += (w < wave) ? (uint32_t)sMisc[w] : 0u;
+        total += (uint32_t)sMisc[w];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (fa[j] >= 0) {
+            mDot[at] = sRow[fa[j]];
+            mA[at] = fa[j];
+            mB[at] = (int)(4 * tid + j);
+            mDist[at] = rowDist[fa[j]];
+            at++;
+        }
+    }
+    __syncthreads();
+    // order: dot descending, then cur key ascending (the list is in cur key order); keep the first 128
+    for (uint32_t j = tid; j < total; j += MATCH_WG) {
+        const int d = mDot[j];
+        uint32_t rank = 0;
+        for (uint32_t k = 0; k < total; k++) rank += (mDot[k] > d || (mDot[k] == d && k < j)) ? 1u : 0u;
+        if (rank < RAW) {
+            oIdx[rank] = make_uint2(prevOff + (uint32_t)mA[j], curOff + (uint32_t)mB[j]);
+            oDist[rank] = mDist[j];
+        }
+    }
+    if (tid < RAW && tid >= total) {
+        oIdx[tid] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        oDist[tid] = 999.0f;
+    }
+    if (tid == 0) A.rawCount[prev] = total;
+}
+
+// byte sum of every descriptor of an image
+__global__ void k_desc_sums(const uint8_t* descs, int32_t* sums, uint32_t first, uint32_t n) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint4* d = (const uint4*)(descs + (size_t)(first + k) * 128);
+    uint32_t s = 0;
+    for (int i = 0; i < 8; i++) {
+        const uint4 v = d[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        for (int j = 0; j < 4; j++) s += (w[j] & 0xFF) + ((w[j] >> 8) & 0xFF) + ((w[j] >> 16) & 0xFF) + (w[j] >> 24);
+    }
+    sums[first + k] = (int32_t)s;
+}
+
+// ---- FilterKeyPointMatchesCU ------------------------------------------------------------------------------
+struct FilterArgs {
+    const BFSiftKeyPoint* keys;
+    const uint32_t* rawCount;
+    const uint2* rawIdx;
+    const float* rawDist;
+    uint32_t* filtCount;
+    uint2* filtIdx;
+    float* filtDist;
+    float* T;
+    float* Tinv;
+    float kinv[16];
+    uint32_t cur, start, minNumMatches;
+    float maxRes2;
+};
+
+// float4x4 * float3 with w = 1 (cuda_SimpleMatrixUtil.h:937-945)
+__device__ __forceinline__ void xform3(const float* e, float x, float y, float z, float* o) {
+    o[0] = e[0] * x + e[1] * y + e[2] * z + e[3] * 1.0f;
+    o[1] = e[4] * x + e[5] * y + e[6] * z + e[7] * 1.0f;
+    o[2] = e[8] * x + e[9] * y + e[10] * z + e[11] * 1.0f;
+}
+
+// camera-space point of a key: intrinsicsInv * (depth * (x, y, 1))
+__device__ __forceinline__ void key_point(const float* kinv, const BFSiftKeyPoint& k, float* o) {
+    xform3(kinv, k.depth * k.x, k.depth * k.y, k.depth * 1.0f, o);
+}
+
+// cyclic Jacobi on a symmetric 3x3: a -> diagonal (eigenvalues), V's columns the eigenvectors
+__device__ void jacobi3(double a[3][3], double V[3][3]) {
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 12; sweep++) {
+        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+        if (off == 0.0) break;
+#pragma unroll
+        for (int pq = 0; pq < 3; pq++) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+            if (a[p][q] == 0.0) continue;
+            const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double akp = a[k][p], akq = a[k][q];
+                a[k][p] = c * akp - s * akq;
+                a[k][q] = s * akp + c * akq;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double apk = a[p][k], aqk = a[q][k];
+                a[p][k] = c * apk - s * aqk;
+                a[q][k] = s * apk + c * aqk;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double vkp = V[k][p], vkq = V[k][q];
+                V[k][p] = c * vkp - s * vkq;
+                V[k][q] = s * vkp + c * vkq;
+            }
+        }
+    }
+}
+
+// largest / second eigenvalue of the covariance of n points (covarianceSVD, cuda_kabsch.h:213-229)
+__device__ double cov_ratio(const float* pts, uint32_t n) {
+    double m[3] = {0, 0, 0};
+    for (uint32_t i = 0; i < n; i++)
+        for (int r = 0; r < 3; r++) m[r] += (double)pts[3 * i + r];
+    for (int r = 0; r < 3; r++) m[r] /= (double)n;
+    double C[3][3] = {};
+    for (uint32_t i = 0; i < n; i++) {
+        const double d[3] = {pts[3 * i] - m[0], pts[3 * i + 1] - m[1], pts[3 * i + 2] - m[2]};
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) C[r][c] += d[r] * d[c];
+    }
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) C[r][c] /= (double)n;
+    double V[3][3];
+    jacobi3(C, V);
+    double e0 = C[0][0], e1 = C[1][1], e2 = C[2][2], t;
+    if (e0 < e1) { t = e0; e0 = e1; e1 = t; }
+    if (e1 < e2) { t = e1; e1 = e2; e2 = t; }
+    if (e0 < e1) { t = e0; e0 = e1; e1 = t; }
+    return e0 / e1;
+}
+
+// kabsch (cuda_kabsch.h:73-211): rigid transform src -> tgt; *c1 = largest / second singular value of the
+// cross-covariance. The reflection case flips the direction of the smallest singular value.
+__device__ void kabsch(const float* src, const float* tgt, uint32_t n, float* T, double* c1) {
+    double p0[3] = {0, 0, 0}, q0[3] = {0, 0, 0};
+    for (uint32_t i = 0; i < n; i++)
+        for (int r = 0; r < 3; r++) {
+            p0[r] += (double)src[3 * i + r];
+            q0[r] += (double)tgt[3 * i + r];
+        }
+    for (int r = 0; r < 3; r++) {
+        p0[r] /= (double)n;
+        q0[r] /= (double)n;
+    }
+    double H[3][3] = {};
+    for (uint32_t i = 0; i < n; i++) {
+        const double dp[3] = {src[3 * i] - p0[0], src[3 * i + 1] - p0[1], src[3 * i + 2] - p0[2]};
+        const double dq[3] = {tgt[3 * i] - q0[0], tgt[3 * i + 1] - q0[1], tgt[3 * i + 2] - q0[2]};
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) H[r][c] += dp[r] * dq[c];
+    }
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) H[r][c] /= (double)n;
+    // H = U S W^T: W from the eigenvectors of H^T H, U = H W / S
+    double M[3][3], W[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) M[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
+    jacobi3(M, W);
+    double ev[3] = {M[0][0], M[1][1], M[2][2]};
+    int o0 = 0, o1 = 1, o2 = 2, ti;
+    if (ev[o0] < ev[o1]) { ti = o0; o0 = o1; o1 = ti; }
+    if (ev[o1] < ev[o2]) { ti = o1; o1 = o2; o2 = ti; }
+    if (ev[o0] < ev[o1]) { ti = o0; o0 = o1; o1 = ti; }
+    double w1[3], w2[3], w3[3], u1[3], u2[3], u3[3];
+    for (int r = 0; r < 3; r++) {
+        w1[r] = o0 == 0 ? W[r][0] : (o0 == 1 ? W[r][1] : W[r][2]);
+        w2[r] = o1 == 0 ? W[r][0] : (o1 == 1 ? W[r][1] : W[r][2]);
+    }
+    const double l1 = o0 == 0 ? ev[0] : (o0 == 1 ? ev[1] : ev[2]), l2 = o1 == 0 ? ev[0] : (o1 == 1 ? ev[1] : ev[2]);
+    *c1 = sqrt(fmax(l1, 0.0)) / sqrt(fmax(l2, 0.0));
+    for (int r = 0; r < 3; r++) {
+        u1[r] = H[r][0] * w1[0] + H[r][1] * w1[1] + H[r][2] * w1[2];
+        u2[r] = H[r][0] * w2[0] + H[r][1] * w2[1] + H[r][2] * w2[2];
+    }
+    double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+    if (n1 > 0.0) {
+        for (int r = 0; r < 3; r++) u1[r] /= n1;
+    } else {
+        u1[0] = 1.0; u1[1] = 0.0; u1[2] = 0.0;
+    }
+    double d12 = u2[0] * u1[0] + u2[1] * u1[1] + u2[2] * u1[2];
+    for (int r = 0; r < 3; r++) u2[r] -= d12 * u1[r];
+    double n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    if (n2 > 1e-150) {
+        for (int r = 0; r < 3; r++) u2[r] /= n2;
+    } else {  // rank <= 1 (rejected by the condition test): any unit vector orthogonal to u1
+        const int m = fabs(u1[0]) <= fabs(u1[1]) ? (fabs(u1[0]) <= fabs(u1[2]) ? 0 : 2) : (fabs(u1[1]) <= fabs(u1[2]) ? 1 : 2);
+        double e[3] = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
+        d12 = e[0] * u1[0] + e[1] * u1[1] + e[2] * u1[2];
+        for (int r = 0; r < 3; r++) u2[r] = e[r] - d12 * u1[r];
+        n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+        for (int r = 0; r < 3; r++) u2[r] /= n2;
+    }
+    u3[0] = u1[1] * u2[2] - u1[2] * u2[1]; u3[1] = u1[2] * u2[0] - u1[0] * u2[2]; u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+    w3[0] = w1[1] * w2[2] - w1[2] * w2[1]; w3[1] = w1[2] * w2[0] - w1[0] * w2[2]; w3[2] = w1[0] * w2[1] - w1[1] * w2[0];
+    double R[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) R[r][c] = w1[r] * u1[c] + w2[r] * u2[c] + w3[r] * u3[c];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) T[4 * r + c] = (float)R[r][c];
+        T[4 * r + 3] = (float)(q0[r] - (R[r][0] * p0[0] + R[r][1] * p0[1] + R[r][2] * p0[2]));
+    }
+    T[12] = 0.0f; T[13] = 0.0f; T[14] = 0.0f; T[15] = 1.0f;
+}
+
+struct FilterLds {
+    uint2 idx[RAW];
+    float dist[RAW];
+    float src[3 * FILT], tgt[3 * FILT], res[FILT];
+};
+
+// ComputeReprojection (cuda_kabsch.h:380-412)
+__device__ bool compute_reprojection(FilterLds& L, uint32_t n, float* T) {
+    double c1;
+    kabsch(L.src, L.tgt, n, T, &c1);
+    for (uint32_t i = 0; i < n; i++) {
+        float p[3];
+        xform3(T, L.src[3 * i], L.src[3 * i + 1], L.src[3 * i + 2], p);
+        const float dx = p[0] - L.tgt[3 * i], dy = p[1] - L.tgt[3 * i + 1], dz = p[2] - L.tgt[3 * i + 2];
+        L.res[i] = dx * dx + dy * dy + dz * dz;
+    }
+    // sortKabschResiduals: exchange sort, points / indices / distances along
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = i; j < n; j++)
+            if (L.res[i] > L.res[j]) {
+                float t = L.res[i]; L.res[i] = L.res[j]; L.res[j] = t;
+                for (int r = 0; r < 3; r++) {
+                    t = L.src[3 * i + r]; L.src[3 * i + r] = L.src[3 * j + r]; L.src[3 * j + r] = t;
+                    t = L.tgt[3 * i + r]; L.tgt[3 * i + r] = L.tgt[3 * j + r]; L.tgt[3 * j + r] = t;
+                }
+                const uint2 ti = L.idx[i]; L.idx[i] = L.idx[j]; L.idx[j] = ti;
+                t = L.dist[i]; L.dist[i] = L.dist[j]; L.dist[j] = t;
+            }
+    const double cp = cov_ratio(L.src, n), cq = cov_ratio(L.tgt, n);
+    if (isnan(c1) || isnan(cp) || isnan(cq) || fabs(c1) > 100.0 || fabs(cp) > 100.0 || fabs(cq) > 100.0) return false;
+    return true;
+}
+
+// filterKeyPointMatches (cuda_kabsch.h:422-502) on the raw list in L (sorted by distance); returns the kept count
+__device__ uint32_t filter_matches(FilterLds& L, const BFSiftKeyPoint* keys, uint32_t numRaw, float* T, const float* kinv,
+                                   uint32_t minNumMatches, float maxRes) {
+    uint32_t idx = 0, cur = 0;
+    float curMaxResidual = 100.0f;
+    bool validTransform = false;
+    for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+    while (true) {
+        if (idx == numRaw || cur >= FILT) {
+            if (cur < minNumMatches || curMaxResidual >= maxRes || !validTransform) cur = 0;
+            break;
+        }
+        // addMatch (cuda_kabsch.h:281-295): 5-pixel rejection against the kept matches in either image
+        const uint2 add = L.idx[idx];
+        bool ok = true;
+        {
+            const BFSiftKeyPoint ai = keys[add.x], aj = keys[add.y];
+            for (uint32_t i = 0; i < cur && ok; i++) {
+                const BFSiftKeyPoint ki = keys[L.idx[i].x], kj = keys[L.idx[i].y];
+                const float dix = ai.x - ki.x, diy = ai.y - ki.y, djx = aj.x - kj.x, djy = aj.y - kj.y;
+                if (sqrtf(dix * dix + diy * diy) <= 5.0f || sqrtf(djx * djx + djy * djy) <= 5.0f) ok = false;
+            }
+        }
+        if (ok) {
+            L.idx[cur] = add;
+            L.dist[cur] = L.dist[idx];
+            cur++;
+            if (cur >= 3) {
+                for (uint32_t i = 0; i < cur; i++) {
+                    key_point(kinv, keys[L.idx[i].x], &L.src[3 * i]);
+                    key_point(kinv, keys[L.idx[i].y], &L.tgt[3 * i]);
+                }
+                validTransform = compute_reprojection(L, cur, T);
+                const bool b = validTransform;
+                float prevT[16];
+                for (int k = 0; k < 16; k++) prevT[k] = T[k];
+                curMaxResidual = L.res[cur - 1];
+                if (curMaxResidual > maxRes) {  // some bad matches: remove the largest until below
+                    float lastRes = -1.0f;
+                    const int startIdx = (int)cur - 1;
+                    for (int i = startIdx; i >= 3; i--) {
+                        lastRes = L.res[i];
+                        cur--;
+                        validTransform = compute_reprojection(L, cur, T);
+                        curMaxResidual = L.res[cur - 1];
+                        if (cur == 3 && (curMaxResidual > maxRes || (b && !validTransform))) {
+                            cur++;  // removing made it worse: restore
+                            curMaxResidual = lastRes;
+                            validTransform = b;
+                            for (int k = 0; k < 16; k++) T[k] = prevT[k];
+                            break;
+                        }
+                        if (curMaxResidual < maxRes) break;
+                    }
+                }
+            }
+        }
+        idx++;
+    }
+    return cur;
+}
+
+__global__ __launch_bounds__(64) void k_filter(FilterArgs A) {
+    __shared__ FilterLds L;
+    __shared__ uint32_t sKept;
+    __shared__ float sT[16];
+    const uint32_t prev = A.start + blockIdx.x;
+    if (prev == A.cur) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t numRaw = min(RAW, A.rawCount[prev]);
+    for (uint32_t k = tid; k < RAW; k += 64) {
+        L.idx[k] = k < numRaw ? A.rawIdx[(size_t)prev * RAW + k] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        L.dist[k] = k < numRaw ? A.rawDist[(size_t)prev * RAW + k] : 999.0f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float T[16];
+        for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+        sKept = numRaw ? filter_matches(L, A.keys, numRaw, T, A.kinv, A.minNumMatches, A.maxRes2) : 0u;
+        for (int k = 0; k < 16; k++) sT[k] = T[k];
+    }
+    __syncthreads();
+    const uint32_t kept = sKept;
+    if (tid == 0) A.filtCount[prev] = kept;
+    if (tid < FILT) {
+        A.filtIdx[(size_t)prev * FILT + tid] = tid < kept ? L.idx[tid] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        A.filtDist[(size_t)prev * FILT + tid] = tid < kept ? L.dist[tid] : 999.0f;
+    }
+    if (tid < 16) A.T[16 * (size_t)prev + tid] = sT[tid];
+    if (tid < 16) {  // rigid inverse [R^T | -R^T t]
+        const uint32_t r = tid >> 2, c = tid & 3;
+        float v;
+        if (r == 3) {
+            v = c == 3 ? 1.0f : 0.0f;
+        } else if (c < 3) {
+            v = sT[4 * c + r];
+        } else {
+            v = (float)(-((double)sT[r] * sT[3] + (double)sT[4 + r] * sT[7] + (double)sT[8 + r] * sT[11]));
+        }
+        A.Tinv[16 * (size_t)prev + tid] = v;
+    }
+}
+
+// ---- AddCurrToResidualsCU ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(32) void k_add_residuals(const BFSiftKeyPoint* keys, const uint32_t* filtCount, const uint2* filtIdx,
+                                                      const uint32_t* base, uint32_t cur, uint32_t start, BFEntryJ* out,
+                                                      uint32_t* keyIdx, uint32_t cap, const float* kinvDev) {
+    const uint32_t prev = start + blockIdx.x;
+    if (prev == cur) return;
+    const uint32_t n = filtCount[prev], t = threadIdx.x, at = base[prev] + t;
+    if (t >= n || at >= cap) return;
+    const uint2 ij = filtIdx[(size_t)prev * FILT + t];
+    float kinv[16];
+    for (int k = 0; k < 16; k++) kinv[k] = kinvDev[k];
+    float pi[3], pj[3];
+    key_point(kinv, keys[ij.x], pi);
+    key_point(kinv, keys[ij.y], pj);
+    BFEntryJ e;
+    e.imgIdx_i = prev;
+    e.imgIdx_j = cur;
+    e.pos_i.x = pi[0]; e.pos_i.y = pi[1]; e.pos_i.z = pi[2];
+    e.pos_j.x = pj[0]; e.pos_j.y = pj[1]; e.pos_j.z = pj[2];
+    out[at] = e;
+    if (keyIdx) {
+        keyIdx[2 * (size_t)at] = ij.x;
+        keyIdx[2 * (size_t)at + 1] = ij.y;
+    }
+}
+
+}  // namespace
+
+MatcherConfig make_matcher_config(const BFMatcherOptions* o) {
+    BF_REQUIRE(o != nullptr, BF_ERR_ARG, "null matcher options");
+    BF_REQUIRE(o->maxImages > 0 && o->maxKeysPerImage > 0, BF_ERR_ARG, "matcher capacity: maxImages / maxKeysPerImage are 0");
+    BF_REQUIRE(o->maxKeysPerImage <= BF_MATCH_MAX_KEYS_PER_IMAGE, BF_ERR_ARG, "maxKeysPerImage above 1024");
+    BF_REQUIRE((uint64_t)o->maxImages * o->maxKeysPerImage <= (1ull << 28), BF_ERR_ARG, "matcher capacity too large");
+    BF_REQUIRE(std::isfinite(o->matchThresh) && std::isfinite(o->ratioMax) && std::isfinite(o->maxKabschRes2) &&
+                   o->matchThresh >= 0.0f && o->ratioMax >= 0.0f && o->maxKabschRes2 >= 0.0f,
+               BF_ERR_ARG, "matcher options: non-finite or negative threshold");
+    MatcherConfig c;
+    c.maxImages = o->maxImages;
+    c.maxKeys = o->maxKeysPerImage;
+    c.matchThresh = o->matchThresh > 0.0f ? o->matchThresh : 0.7f;
+    c.ratioMax = o->ratioMax > 0.0f ? o->ratioMax : 0.8f;
+    c.minNumMatches = o->minNumMatches ? o->minNumMatches : 5u;
+    c.maxKabschRes2 = o->maxKabschRes2 > 0.0f ? o->maxKabschRes2 : 0.0004f;
+    bool any = false;
+    for (int k = 0; k < 16; k++) {
+        BF_REQUIRE(std::isfinite(o->intrinsicsInv[k]), BF_ERR_ARG, "matcher options: non-finite intrinsicsInv");
+        any = any || o->intrinsicsInv[k] != 0.0f;
+        c.kinv[k] = o->intrinsicsInv[k];
+    }
+    if (!any)
+        for (int k = 0; k < 16; k++) c.kinv[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+    return c;
+}
+
+Matcher::Matcher(const MatcherConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(stream) {
+    const size_t keys = (size_t)cfg.maxImages * cfg.maxKeys, n = cfg.maxImages;
+    keys_.alloc(keys);
+    descs_.alloc(keys * 128);
+    sums_.alloc(keys);
+    table_.alloc(4 * n);
+    rawCount_.alloc(n);
+    filtCount_.alloc(n);
+    rawIdx_.alloc(n * kRaw);
+    rawDist_.alloc(n * kRaw);
+    filtIdx_.alloc(n * kFilt);
+    filtDist_.alloc(n * kFilt);
+    T_.alloc(16 * n);
+    Tinv_.alloc(16 * n);
+    base_.alloc(n + 16);  // + intrinsicsInv (16 floats) behind the bases
+    dbgSel_.alloc(2 * kDbg);
+    dbgOut_.alloc(kDbg * kDbg + 3 * kDbg);
+    BF_HIP(hipHostMalloc((void**)&hostTable_, 4 * n * sizeof(uint32_t), hipHostMallocDefault));
+    BF_HIP(hipHostMalloc((void**)&hostCounts_, n * sizeof(uint32_t), hipHostMallocDefault));
+    BF_HIP(hipHostMalloc((void**)&hostBase_, (n + 16) * sizeof(uint32_t), hipHostMallocDefault));
+    BF_HIP(hipFuncSetAttribute((const void*)k_match<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MATCH_LDS_BYTES));
+    BF_HIP(hipFuncSetAttribute((const void*)k_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MATCH_LDS_BYTES));
+    std::memcpy(hostBase_ + n, cfg_.kinv, 64);
+    BF_HIP(hipMemcpyAsync(base_.p + n, hostBase_ + n, 64, hipMemcpyHostToDevice, stream_));
+    reset();
+}
+
+Matcher::~Matcher() {
+    if (hostTable_) (void)hipHostFree(hostTable_);
+    if (hostCounts_) (void)hipHostFree(hostCounts_);
+    if (hostBase_) (void)hipHostFree(hostBase_);
+}
+
+void Matcher::reset() {
+    num_.clear();
+    off_.clear();
+    valid_.clear();
+    totalKeys_ = 0;
+    tableDirty_ = true;
+    const size_t n = cfg_.maxImages;
+    BF_HIP(hipMemsetAsync(rawCount_.p, 0, n * 4, stream_));
+    BF_HIP(hipMemsetAsync(filtCount_.p, 0, n * 4, stream_));
+    BF_HIP(hipMemsetAsync(rawIdx_.p, 0xFF, rawIdx_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(filtIdx_.p, 0xFF, filtIdx_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(rawDist_.p, 0, rawDist_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(filtDist_.p, 0, filtDist_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(T_.p, 0, T_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(Tinv_.p, 0, Tinv_.bytes(), stream_));
+}
+
+uint32_t Matcher::addImage(const BFSiftKeyPoint* keys, const uint8_t* descs, uint32_t n) {
+    BF_REQUIRE(n <= cfg_.maxKeys, BF_ERR_ARG, "more keys than maxKeysPerImage");
+    BF_REQUIRE(n == 0 || (keys && descs), BF_ERR_ARG, "null keys / descriptors");
+    BF_REQUIRE(num_.size() < cfg_.maxImages, BF_ERR_CAPACITY, "matcher image store is full");
+    const uint32_t index = (uint32_t)num_.size();
+    if (n) {
+        BF_HIP(hipMemcpyAsync(keys_.p + totalKeys_, keys, (size_t)n * sizeof(BFSiftKeyPoint), hipMemcpyDeviceToDevice, stream_));
+        BF_HIP(hipMemcpyAsync(descs_.p + (size_t)totalKeys_ * 128, descs, (size_t)n * 128, hipMemcpyDeviceToDevice, stream_));
+        k_desc_sums<<<div_up(n, 128), 128, 0, stream_>>>(descs_.p, sums_.p, totalKeys_, n);
+        BF_LAUNCH_CHECK();
+    }
+    num_.push_back(n);
+    off_.push_back(totalKeys_);
+    valid_.push_back(index == 0 ? 1 : 0);  // image 0 starts valid; filterFrames decides the others
+    totalKeys_ += n;
+    tableDirty_ = true;
+    return index;
+}
+
+void Matcher::setValid(uint32_t i, int v) {
+    valid_[i] = v ? 1 : 0;
+    tableDirty_ = true;
+}
+
+void Matcher::uploadTable() {
+    if (!tableDirty_) return;
+    BF_HIP(hipStreamSynchronize(stream_));  // an earlier upload may still read the pinned table
+    const uint32_t n = numImages();
+    for (uint32_t i = 0; i < n; i++) {
+        hostTable_[4 * i] = off_[i];
+        hostTable_[4 * i + 1] = num_[i];
+        hostTable_[4 * i + 2] = (uint32_t)valid_[i];
+        hostTable_[4 * i + 3] = 0;
+    }
+    if (n) BF_HIP(hipMemcpyAsync(table_.p, hostTable_, 16 * (size_t)n, hipMemcpyHostToDevice, stream_));
+    tableDirty_ = false;
+}
+
+void Matcher::launchMatch(uint32_t cur, uint32_t start, uint32_t pairs, bool debug, uint32_t nRows, uint32_t nCols) {
+    MatchArgs A{};
+    A.descs = descs_.p;
+    A.sums = sums_.p;
+    A.table = table_.p;
+    A.cur = cur;
+    A.start = start;
+    A.thresh = cfg_.matchThresh;
+    A.ratio = cfg_.ratioMax;
+    A.rawCount = rawCount_.p;
+    A.rawIdx = rawIdx_.p;
+    A.rawDist = rawDist_.p;
+    A.dbgSel = dbgSel_.p;
+    A.dbgOut = dbgOut_.p;
+    A.dbgRows = nRows;
+    A.dbgCols = nCols;
+    if (debug)
+        k_match<true><<<pairs, MATCH_WG, MATCH_LDS_BYTES, stream_>>>(A);
+    else
+        k_match<false><<<pairs, MATCH_WG, MATCH_LDS_BYTES, stream_>>>(A);
+    BF_LAUNCH_CHECK();
+}
+
+void Matcher::match(uint32_t cur, uint32_t start) {
+    const uint32_t n = numImages();
+    BF_REQUIRE(cur < n, BF_ERR_ARG, "curFrame >= numImages");
+    BF_REQUIRE(start <= n, BF_ERR_ARG, "startFrame > numImages");
+    if (start == n) return;
+    uploadTable();
+    launchMatch(cur, start, n - start, false, 0, 0);
+}
+
+void Matcher::filter(uint32_t cur, uint32_t start) {
+    const uint32_t n = numImages();
+    BF_REQUIRE(cur < n, BF_ERR_ARG, "curFrame >= numImages");
+    BF_REQUIRE(start <= n, BF_ERR_ARG, "startFrame > numImages");
+    if (start == n) return;
+    FilterArgs A{};
+    A.keys = keys_.p;
+    A.rawCount = rawCount_.p;
+    A.rawIdx = rawIdx_.p;
+    A.rawDist = rawDist_.p;
+    A.filtCount = filtCount_.p;
+    A.filtIdx = filtIdx_.p;
+    A.filtDist = filtDist_.p;
+    A.T = T_.p;
+    A.Tinv = Tinv_.p;
+    for (int k = 0; k < 16; k++) A.kinv[k] = cfg_.kinv[k];
+    A.cur = cur;
+    A.start = start;
+    A.minNumMatches = cfg_.minNumMatches;
+    A.maxRes2 = cfg_.maxKabschRes2;
+    k_filter<<<n - start, 64, 0, stream_>>>(A);
+    BF_LAUNCH_CHECK();
+}
+
+uint32_t Matcher::filterFrames(uint32_t cur, uint32_t start) {
+    const uint32_t n = numImages();
+    BF_REQUIRE(cur < n, BF_ERR_ARG, "curFrame >= numImages");
+    BF_REQUIRE(start <= n, BF_ERR_ARG, "startFrame > numImages");
+    uint32_t last = 0xFFFFFFFFu;
+    if (start < n) {
+        BF_HIP(hipMemcpyAsync(hostCounts_, filtCount_.p + start, 4 * (size_t)(n - start), hipMemcpyDeviceToHost, stream_));
+        BF_HIP(hipStreamSynchronize(stream_));
+        for (int i = (int)n - 1; i >= (int)start; i--)
+            if (valid_[i] != 0 && hostCounts_[i - start] > 0 && (uint32_t)i != cur) {
+                last = (uint32_t)i;
+                break;
+            }
+    }
+    setValid(cur, last != 0xFFFFFFFFu);
+    return last;
+}
+
+uint32_t Matcher::addToResiduals(uint32_t cur, uint32_t start, BFEntryJ* out, uint32_t* keyIdx, uint32_t cap, uint32_t* total) {
+    const uint32_t n = numImages();
+    BF_REQUIRE(cur < n, BF_ERR_ARG, "curFrame >= numImages");
+    BF_REQUIRE(start <= n, BF_ERR_ARG, "startFrame > numImages");
+    BF_REQUIRE(out != nullptr || cap == 0, BF_ERR_ARG, "null output");
+    if (total) *total = 0;
+    if (start == n) return 0;
+    BF_HIP(hipMemcpyAsync(hostCounts_, filtCount_.p + start, 4 * (size_t)(n - start), hipMemcpyDeviceToHost, stream_));
+    BF_HIP(hipStreamSynchronize(stream_));
+    uint32_t sum = 0;
+    for (uint32_t i = start; i < n; i++) {
+        hostBase_[i] = sum;
+        if (i != cur) sum += hostCounts_[i - start];
+    }
+    if (total) *total = sum;
+    if (sum && cap) {
+        BF_HIP(hipMemcpyAsync(base_.p + start, hostBase_ + start, 4 * (size_t)(n - start), hipMemcpyHostToDevice, stream_));
+        k_add_residuals<<<n - start, 32, 0, stream_>>>(keys_.p, filtCount_.p, filtIdx_.p, base_.p, cur, start, out, keyIdx, cap,
+                                                      (const float*)(base_.p + cfg_.maxImages));
+        BF_LAUNCH_CHECK();
+        BF_HIP(hipStreamSynchronize(stream_));
+    }
+    return sum < cap ? sum : cap;
+}
+
+void Matcher::rawMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist) {
+    BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
+    BF_HIP(hipStreamSynchronize(stream_));
+    if (count) BF_HIP(hipMemcpy(count, rawCount_.p + prev, 4, hipMemcpyDeviceToHost));
+    if (idx) BF_HIP(hipMemcpy(idx, rawIdx_.p + (size_t)prev * kRaw, 8 * kRaw, hipMemcpyDeviceToHost));
+    if (dist) BF_HIP(hipMemcpy(dist, rawDist_.p + (size_t)prev * kRaw, 4 * kRaw, hipMemcpyDeviceToHost));
+}
+
+void Matcher::filteredMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist) {
+    BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
+    BF_HIP(hipStreamSynchronize(stream_));
+    if (count) BF_HIP(hipMemcpy(count, filtCount_.p + prev, 4, hipMemcpyDeviceToHost));
+    if (idx) BF_HIP(hipMemcpy(idx, filtIdx_.p + (size_t)prev * kFilt, 8 * kFilt, hipMemcpyDeviceToHost));
+    if (dist) BF_HIP(hipMemcpy(dist, filtDist_.p + (size_t)prev * kFilt, 4 * kFilt, hipMemcpyDeviceToHost));
+}
+
+void Matcher::transforms(uint32_t prev, float* T, float* Tinv) {
+    BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
+    BF_HIP(hipStreamSynchronize(stream_));
+    if (T) BF_HIP(hipMemcpy(T, T_.p + 16 * (size_t)prev, 64, hipMemcpyDeviceToHost));
+    if (Tinv) BF_HIP(hipMemcpy(Tinv, Tinv_.p + 16 * (size_t)prev, 64, hipMemcpyDeviceToHost));
+}
+
+void Matcher::debugDots(uint32_t prev, uint32_t cur, const uint32_t* rows, uint32_t nRows, const uint32_t* cols, uint32_t nCols,
+                        int32_t* dots, int32_t* rowStats) {
+    const uint32_t n = numImages();
+    BF_REQUIRE(prev < n && cur < n && prev != cur, BF_ERR_ARG, "prev / curFrame out of range or equal");
+    BF_REQUIRE(nRows <= kDbg && nCols <= kDbg && (rows || nRows == 0) && (cols || nCols == 0), BF_ERR_ARG,
+               "at most 32 rows and 32 columns");
+    for (uint32_t r = 0; r < nRows; r++) BF_REQUIRE(rows[r] < num_[prev], BF_ERR_ARG, "row >= prev's key count");
+    for (uint32_t c = 0; c < nCols; c++) BF_REQUIRE(cols[c] < num_[cur], BF_ERR_ARG, "column >= curFrame's key count");
+    uploadTable();
+    uint32_t sel[2 * kDbg] = {};
+    for (uint32_t r = 0; r < nRows; r++) sel[r] = rows[r];
+    for (uint32_t c = 0; c < nCols; c++) sel[kDbg + c] = cols[c];
+    BF_HIP(hipMemcpyAsync(dbgSel_.p, sel, sizeof(sel), hipMemcpyHostToDevice, stream_));  // pageable: staged before it returns
+    BF_HIP(hipMemsetAsync(dbgOut_.p, 0, dbgOut_.bytes(), stream_));
+    launchMatch(cur, prev, 1, true, nRows, nCols);
+    BF_HIP(hipStreamSynchronize(stream_));
+    if (dots && nRows * nCols) BF_HIP(hipMemcpy(dots, dbgOut_.p, 4 * (size_t)nRows * nCols, hipMemcpyDeviceToHost));
+    if (rowStats && nRows) BF_HIP(hipMemcpy(rowStats, dbgOut_.p + kDbg * kDbg, 12 * (size_t)nRows, hipMemcpyDeviceToHost));
+}
+
+}  // namespace bf

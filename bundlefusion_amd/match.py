@@ -1,0 +1,153 @@
+"""Python binding of the sparse matcher (bf_matcher_*): the matching side of SIFTImageManager + SiftMatchCU +
+Bundler::matchAndFilter. Key points and 128-byte descriptors in, EntryJ and pair transforms out."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import DeviceArray, check, lib
+from .abi import (ENTRYJ_DTYPE, MAX_MATCHES_FILTERED, MAX_MATCHES_RAW, SIFT_KEYPOINT_DTYPE, BFMatcherOptions)
+
+NO_FRAME = 0xFFFFFFFF
+
+
+def matcher_options(max_images: int, max_keys_per_image: int = 1024, intrinsics_inv=None, match_thresh=0.7,
+                    ratio_max=0.8, min_num_matches=5, max_kabsch_res2=0.0004) -> BFMatcherOptions:
+    """Defaults are zParametersBundlingDefault.txt's; intrinsics_inv: row-major 4x4 inverse colour intrinsics."""
+    o = BFMatcherOptions()
+    o.maxImages, o.maxKeysPerImage = max_images, max_keys_per_image
+    o.matchThresh, o.ratioMax, o.minNumMatches, o.maxKabschRes2 = match_thresh, ratio_max, min_num_matches, max_kabsch_res2
+    k = np.eye(4, dtype=np.float32) if intrinsics_inv is None else np.asarray(intrinsics_inv, np.float32).reshape(4, 4)
+    o.intrinsicsInv[:] = k.ravel().tolist()
+    return o
+
+
+class Matcher:
+    """SIFTImageManager's image store + matchAndFilter over bf_matcher_* (all buffers device-resident)."""
+
+    def __init__(self, opts: BFMatcherOptions):
+        self.h = C.c_void_p()
+        check(lib().bf_matcher_create(C.byref(opts), C.byref(self.h)))
+        self.opts = opts
+
+    def close(self):
+        if self.h:
+            lib().bf_matcher_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib().bf_matcher_reset(self.h))
+
+    def add_image(self, keys: np.ndarray, descs: np.ndarray) -> int:
+        """keys: [n] SIFT_KEYPOINT_DTYPE or [n, 4] float32 (x, y, scale, depth); descs: [n, 128] uint8 (host)."""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype != SIFT_KEYPOINT_DTYPE:
+            keys = np.ascontiguousarray(keys, np.float32).reshape(-1, 4).view(SIFT_KEYPOINT_DTYPE).reshape(-1)
+        descs = np.ascontiguousarray(descs, np.uint8).reshape(-1, 128)
+        n = len(keys)
+        assert len(descs) == n
+        dk = DeviceArray.from_host(keys) if n else None
+        dd = DeviceArray.from_host(descs) if n else None
+        idx = C.c_uint32()
+        check(lib().bf_matcher_add_image(self.h, dk.ptr if n else None, dd.ptr if n else None, C.c_uint32(n), C.byref(idx)))
+        self.synchronize()  # the uploads above may be freed once the matcher has copied them
+        return idx.value
+
+    def add_image_device(self, keys: DeviceArray, descs: DeviceArray, n: int) -> int:
+        idx = C.c_uint32()
+        check(lib().bf_matcher_add_image(self.h, keys.ptr, descs.ptr, C.c_uint32(n), C.byref(idx)))
+        return idx.value
+
+    def num_images(self) -> int:
+        n = C.c_uint32()
+        check(lib().bf_matcher_num_images(self.h, C.byref(n)))
+        return n.value
+
+    def num_keys(self, image: int):
+        """(key count, offset in the linear key array) of an image."""
+        n, off = C.c_uint32(), C.c_uint32()
+        check(lib().bf_matcher_num_keys(self.h, C.c_uint32(image), C.byref(n), C.byref(off)))
+        return n.value, off.value
+
+    def set_valid(self, image: int, valid: bool):
+        check(lib().bf_matcher_set_valid(self.h, C.c_uint32(image), int(bool(valid))))
+
+    def get_valid(self, image: int) -> bool:
+        v = C.c_int()
+        check(lib().bf_matcher_get_valid(self.h, C.c_uint32(image), C.byref(v)))
+        return bool(v.value)
+
+    def match(self, cur: int, start: int = 0):
+        check(lib().bf_matcher_match(self.h, C.c_uint32(cur), C.c_uint32(start)))
+
+    def filter(self, cur: int, start: int = 0):
+        check(lib().bf_matcher_filter(self.h, C.c_uint32(cur), C.c_uint32(start)))
+
+    def filter_frames(self, cur: int, start: int = 0) -> int:
+        last = C.c_uint32()
+        check(lib().bf_matcher_filter_frames(self.h, C.c_uint32(cur), C.c_uint32(start), C.byref(last)))
+        return last.value
+
+    def match_and_filter(self, cur: int, start: int | None = None) -> int:
+        """Bundler::matchAndFilter up to filterFrames; returns lastMatchedFrame (NO_FRAME if none)."""
+        if start is None:
+            start = 0 if self.num_images() == cur + 1 else cur + 1
+        self.match(cur, start)
+        self.filter(cur, start)
+        return self.filter_frames(cur, start)
+
+    def add_to_residuals(self, cur: int, start: int, cap: int, out: DeviceArray | None = None, want_key_indices=False):
+        """(host EntryJ array, total found[, key index pairs [n, 2]])."""
+        out = out if out is not None else DeviceArray((max(cap, 1),), ENTRYJ_DTYPE)
+        kidx = DeviceArray((max(cap, 1), 2), np.uint32) if want_key_indices else None
+        n, total = C.c_uint32(), C.c_uint32()
+        check(lib().bf_matcher_add_to_residuals(self.h, C.c_uint32(cur), C.c_uint32(start), out.ptr,
+                                                kidx.ptr if kidx is not None else None, C.c_uint32(cap), C.byref(n),
+                                                C.byref(total)))
+        res = out.download_range(0, 32 * n.value).view(ENTRYJ_DTYPE).copy() if n.value else np.zeros(0, ENTRYJ_DTYPE)
+        if want_key_indices:
+            k = kidx.download_range(0, 8 * n.value).view(np.uint32).reshape(-1, 2).copy() if n.value else \
+                np.zeros((0, 2), np.uint32)
+            return res, total.value, k
+        return res, total.value
+
+    def _matches(self, fn, prev: int, cap: int):
+        count = C.c_uint32()
+        idx = np.empty((cap, 2), np.uint32)
+        dist = np.empty(cap, np.float32)
+        check(fn(self.h, C.c_uint32(prev), C.byref(count), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p)))
+        return count.value, idx, dist
+
+    def raw_matches(self, prev: int):
+        """(count of mutual matches, idx [128, 2], dist [128]); the first min(count, 128) entries are set."""
+        return self._matches(lib().bf_matcher_raw_matches, prev, MAX_MATCHES_RAW)
+
+    def filtered_matches(self, prev: int):
+        return self._matches(lib().bf_matcher_filtered_matches, prev, MAX_MATCHES_FILTERED)
+
+    def transforms(self, prev: int):
+        """(T prev -> cur, Tinv cur -> prev) as 4x4 float32."""
+        T, Ti = np.empty(16, np.float32), np.empty(16, np.float32)
+        check(lib().bf_matcher_transforms(self.h, C.c_uint32(prev), T.ctypes.data_as(C.c_void_p), Ti.ctypes.data_as(C.c_void_p)))
+        return T.reshape(4, 4), Ti.reshape(4, 4)
+
+    def debug_dots(self, prev: int, cur: int, rows, cols):
+        """(dots int32 [len(rows), len(cols)], row stats int32 [len(rows), 3] = best, second best, argument)."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        cols = np.ascontiguousarray(cols, np.uint32)
+        dots = np.zeros((len(rows), len(cols)), np.int32)
+        stats = np.zeros((len(rows), 3), np.int32)
+        check(lib().bf_matcher_debug_dots(self.h, C.c_uint32(prev), C.c_uint32(cur), rows.ctypes.data_as(C.c_void_p),
+                                          C.c_uint32(len(rows)), cols.ctypes.data_as(C.c_void_p), C.c_uint32(len(cols)),
+                                          dots.ctypes.data_as(C.c_void_p), stats.ctypes.data_as(C.c_void_p)))
+        return dots, stats
+
+    def synchronize(self):
+        check(lib().bf_matcher_synchronize(self.h))

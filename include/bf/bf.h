@@ -28,7 +28,8 @@ extern "C" {
                              4: configuration through the ABI only (BFSceneOptions.applyXcdRun / applyRounds / testFlags /
                              splatRowCap, BFReconOptions.bundlingPriority, bf_set_host_threads; no environment switches),
                              BFSceneCapacity + bf_scene_capacity / bf_recon_scene_capacity (scene errors fail the loop),
-                             bf_recon_set_render (visualizeFrame's render per frame) */
+                             bf_recon_set_render (visualizeFrame's render per frame);
+                             additive, still 4: the sparse matcher (BFSiftKeyPoint, BFMatcherOptions, bf_matcher_*) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -600,6 +601,74 @@ int bf_corr_load(const char* path, BFEntryJ* corr, uint64_t cap, uint64_t* n);
 int bf_corr_from_depth(const float* const* depth, const float* transforms, const float* transformsInv, uint32_t curFrame,
                        uint32_t startFrame, const BFCorrOptions* o, BFEntryJ* out, uint32_t cap, uint32_t* n,
                        uint32_t* total);
+
+/* ---- sparse matcher: the matching side of SIFTImageManager + SiftMatch + Bundler::matchAndFilter ----------
+ * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out (the DoG detector /
+ * descriptor, the surface-area and dense-verify filters, tryRevalidation and fuseToGlobal are not part of it).
+ * Work is queued on the matcher's own stream; the read-backs and bf_matcher_filter_frames / _add_to_residuals
+ * wait for it. No device allocation after bf_matcher_create. Per-pair results are indexed by the earlier image
+ * `prev`, as the reference's d_curr* arrays are, and hold the last bf_matcher_match / _filter.
+ *
+ * One deliberate departure from the reference: its ColMatch kernel appends mutual matches at an atomic counter
+ * (race order), SortKeyPointMatchesCU then sorts by distance, and with more than 128 mutual matches an arbitrary
+ * 128 survive. Here a pair's raw list is ordered by (dot product descending, current key index ascending) -
+ * distance ascending - and the first 128 of that order are kept, so results are bit-deterministic; the raw count
+ * reported is the true number of mutual matches (it may exceed 128). bf_matcher_add_to_residuals likewise writes
+ * pairs in ascending prev order instead of at an atomic base pointer. */
+typedef struct bf_matcher bf_matcher;
+/* SIFTImageManager ctor (SIFTImageManager.cpp:44-83): capacity maxImages x maxKeysPerImage */
+int bf_matcher_create(const BFMatcherOptions* opts, bf_matcher** out);
+int bf_matcher_destroy(bf_matcher* m);
+/* SIFTImageManager::reset: empties the store; image 0 starts valid */
+int bf_matcher_reset(bf_matcher* m);
+/* createSIFTImageGPU + finalizeSIFTImageGPU: DEVICE keys[n], DEVICE uint8 descs[n][128], stored linearly behind the
+ * earlier images' (n = 0 is legal); *index (may be NULL) = the image index. n > maxKeysPerImage: BF_ERR_ARG; a full
+ * store: BF_ERR_CAPACITY. The inputs are read on the matcher's stream: keep them until bf_matcher_synchronize. */
+int bf_matcher_add_image(bf_matcher* m, const BFSiftKeyPoint* keys, const uint8_t* descs, uint32_t n, uint32_t* index);
+int bf_matcher_num_images(bf_matcher* m, uint32_t* n);
+/* getNumKeyPointsPerImage and the image's offset in the linear key array (either may be NULL) */
+int bf_matcher_num_keys(bf_matcher* m, uint32_t image, uint32_t* n, uint32_t* offset);
+/* m_validImages (getValidImages / setValidImage) */
+int bf_matcher_set_valid(bf_matcher* m, uint32_t image, int valid);
+int bf_matcher_get_valid(bf_matcher* m, uint32_t image, int* valid);
+/* Bundler::matchAndFilter's matching loop (Bundler.cpp:117-136) -> SiftMatchCU::GetSiftMatch -> MultiplyDescriptor /
+ * GetRowMatch / GetColMatch (ProgramCU.cu:1634-1936) + SortKeyPointMatchesCU (SIFTImageManager.cu:59-178), for every
+ * pair (prev, curFrame), prev in [startFrame, numImages) \ {curFrame}, as ONE launch: exact int32 descriptor dot
+ * products on the int8 matrix cores, best / second best / argument per row and column, mutual matches with
+ * acosf(min(dot * 2^-18, 1)) < matchThresh and < ratioMax * (second best's), at most 128 per pair in the order above.
+ * A pair whose prev is invalid or either image has no keys gets 0 matches. */
+int bf_matcher_match(bf_matcher* m, uint32_t curFrame, uint32_t startFrame);
+/* FilterKeyPointMatchesCU (SIFTImageManager.cu:182-314) -> filterKeyPointMatches (cuda_kabsch.h:281-502) on the raw
+ * lists of the last bf_matcher_match: greedy 5-pixel rejection, Kabsch + residual sort + condition test, removal of
+ * the largest residuals, at most 25 matches per pair; transform prev -> cur and its inverse per pair. */
+int bf_matcher_filter(bf_matcher* m, uint32_t curFrame, uint32_t startFrame);
+/* SIFTImageManager::filterFrames (SIFTImageManager.cpp:551-575): *lastMatchedFrame = the highest valid image != curFrame
+ * in [startFrame, numImages) with a filtered count > 0, or UINT32_MAX; sets curFrame's valid flag accordingly. */
+int bf_matcher_filter_frames(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, uint32_t* lastMatchedFrame);
+/* AddCurrToResidualsCU (SIFTImageManager.cu:610-687): EntryJ {prev, curFrame, pos_prev, pos_cur} with pos =
+ * intrinsicsInv * (depth * (x, y, 1)) of the filtered matches, pairs in ascending prev order, matches in filtered-list
+ * order, into DEVICE out[cap]; keyIdx (DEVICE uint32[2 * cap] or NULL) receives the key index pairs. *n = records
+ * written (<= cap), *total (may be NULL) = records found. */
+int bf_matcher_add_to_residuals(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, BFEntryJ* out, uint32_t* keyIdx,
+                                uint32_t cap, uint32_t* n, uint32_t* total);
+/* read-backs to HOST of pair (prev, the last curFrame): *count = mutual matches found (may exceed 128);
+ * idx[2 * 128] {prev key, cur key} indices into the linear key array, dist[128]; unused entries are
+ * {UINT32_MAX, UINT32_MAX} / 999 as the reference pads them. Any output may be NULL. */
+int bf_matcher_raw_matches(bf_matcher* m, uint32_t prev, uint32_t* count, uint32_t* idx, float* dist);
+/* ... filtered: idx[2 * 25], dist[25] */
+int bf_matcher_filtered_matches(bf_matcher* m, uint32_t prev, uint32_t* count, uint32_t* idx, float* dist);
+/* d_currFilteredTransforms / d_currFilteredTransformsInv: T maps prev's camera space to cur's, Tinv back (what
+ * computeSiftTransformCU chains, OnlineBundler.cu:6-71: bf_recon_set_frame's Tinc when prev = cur - 1) */
+int bf_matcher_transforms(bf_matcher* m, uint32_t prev, float T[16], float Tinv[16]);
+/* test read-back of the matching kernel's arithmetic for pair (prev, curFrame): exact dots[nRows * nCols] of the
+ * selected key rows of prev x key columns of curFrame (image-local indices, nRows, nCols <= 32) and
+ * rowStats[3 * nRows] {best, second best, argument} of those rows; HOST outputs. Leaves the pair's raw list as
+ * bf_matcher_match would. */
+int bf_matcher_debug_dots(bf_matcher* m, uint32_t prev, uint32_t curFrame, const uint32_t* rows, uint32_t nRows,
+                          const uint32_t* cols, uint32_t nCols, int32_t* dots, int32_t* rowStats);
+int bf_matcher_synchronize(bf_matcher* m);
+int bf_matcher_timer_start(bf_matcher* m, bf_timer* t);
+int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms); /* synchronizes */
 
 /* ---- mesh output: CUDAMarchingCubesHashSDF::saveMesh (CUDAMarchingCubesHashSDF.cpp:48-105) ------
  * Triangle soup (HOST BFMcTriangle[n], e.g. from bf_scene_extract_mesh) -> indexed mesh as saveMesh

@@ -278,9 +278,34 @@ typedef struct BFCorrOptions {
     uint32_t minPerPair;       /* a pair with fewer matches keeps none (s_minNumMatchesLocal / Global [5]); 0 = 1 */
 } BFCorrOptions;
 
+/* SIFTKeyPoint (Source/SiftGPU/SIFTImageManager.h:22-27): pixel position, scale, depth in metres; 16 B. */
+typedef struct BFSiftKeyPoint {
+    float x, y;
+    float scale;
+    float depth;
+} BFSiftKeyPoint;
+
+#define BF_MATCH_DESC_BYTES 128            /* SIFTKeyPointDesc (SIFTImageManager.h:29-31) */
+#define BF_MAX_MATCHES_RAW 128             /* MAX_MATCHES_PER_IMAGE_PAIR_RAW (GlobalDefines.h:8) */
+#define BF_MAX_MATCHES_FILTERED 25         /* MAX_MATCHES_PER_IMAGE_PAIR_FILTERED (GlobalDefines.h:9) */
+#define BF_MATCH_MAX_KEYS_PER_IMAGE 1024   /* s_maxNumKeysPerImage: the matcher kernel's row / column limit */
+
+/* The sparse matcher (bf_matcher_*); zParametersBundlingDefault.txt values in brackets, taken when 0. */
+typedef struct BFMatcherOptions {
+    uint32_t maxImages;         /* image store capacity (s_maxNumImages / s_submapSize + 1) */
+    uint32_t maxKeysPerImage;   /* s_maxNumKeysPerImage [1024], <= BF_MATCH_MAX_KEYS_PER_IMAGE */
+    float matchThresh;          /* s_siftMatchThresh [0.7] */
+    float ratioMax;             /* s_siftMatchRatioMaxLocal / Global [0.8] */
+    uint32_t minNumMatches;     /* s_minNumMatchesLocal / Global [5] */
+    float maxKabschRes2;        /* s_maxKabschResidual2 [0.0004] */
+    float intrinsicsInv[16];    /* row-major inverse colour intrinsics (m_siftIntrinsicsInv); all 0 = identity */
+    uint32_t reserved[2];
+} BFMatcherOptions;
+
 #ifdef __cplusplus
 } /* extern "C" */
 
+static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
 static_assert(sizeof(BFMat4) == 64, "float4x4 is 64 B");
 static_assert(sizeof(BFHashEntry) == 32, "HashEntry is 32 B");
