@@ -18,7 +18,7 @@ from .abi import (BFDepthCameraParams, BFHashParams, BFMarchingCubesParams, BFRa
 
 __all__ = ["lib", "BFError", "DeviceArray", "SceneRepHashSDF", "hash_params", "depth_camera",
            "synth_scene", "synth_pose", "synth_render", "synth_render_host", "mc_params", "mesh_merge", "mesh_save_ply",
-           "Matcher", "matcher_options"]
+           "Matcher", "matcher_options", "CacheFrames", "match_verify_options"]
 
 _lib = None
 
@@ -377,7 +377,7 @@ def synth_render_host(scene: BFSynthScene, T, cam: BFDepthCameraParams, noise_se
 
 
 def __getattr__(name):  # the matcher binding imports this module's helpers, so it is resolved on first use
-    if name in ("Matcher", "matcher_options"):
+    if name in ("Matcher", "matcher_options", "CacheFrames", "match_verify_options"):
         from . import match
         return getattr(match, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -229,9 +229,16 @@ class BFMatcherOptions(C.Structure):  # include/bf/types.h: the sparse matcher (
                 ("intrinsicsInv", C.c_float * 16), ("reserved", C.c_uint32 * 2)]
 
 
+class BFMatchVerifyOptions(C.Structure):  # include/bf/types.h: the surface-area / dense-verify filters (0 = default)
+    _fields_ = [("surfAreaPcaThresh", C.c_float), ("projCorrDistThres", C.c_float), ("projCorrNormalThres", C.c_float),
+                ("verifySiftErrThresh", C.c_float), ("verifySiftCorrThresh", C.c_float), ("sensorDepthMin", C.c_float),
+                ("sensorDepthMax", C.c_float), ("reserved", C.c_uint32)]
+
+
 SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
 MAX_MATCHES_RAW, MAX_MATCHES_FILTERED, MATCH_MAX_KEYS_PER_IMAGE = 128, 25, 1024
 assert C.sizeof(BFSiftKeyPoint) == 16 and SIFT_KEYPOINT_DTYPE.itemsize == 16
+assert C.sizeof(BFMatchVerifyOptions) == 32
 
 
 class BFVoxelOp(C.Structure):  # include/bf/bf.h

@@ -171,6 +171,7 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFCorrOptions", sizeof(BFCorrOptions)},
         {"BFSiftKeyPoint", sizeof(BFSiftKeyPoint)},
         {"BFMatcherOptions", sizeof(BFMatcherOptions)},
+        {"BFMatchVerifyOptions", sizeof(BFMatchVerifyOptions)},
         {"BFCachedFrame", sizeof(BFCachedFrame)},
         {"BFSceneOptions", sizeof(BFSceneOptions)},
         {"BFVoxelOp", sizeof(BFVoxelOp)},
@@ -1317,6 +1318,51 @@ int bf_matcher_debug_dots(bf_matcher* m, uint32_t prev, uint32_t curFrame, const
     BF_TRY
     BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
     m->m->debugDots(prev, curFrame, rows, nRows, cols, nCols, dots, rowStats);
+    BF_CATCH
+}
+int bf_match_filter_surface_area(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFMatchVerifyOptions* opts) {
+    BF_TRY
+    const MatchVerifyConfig v = make_match_verify_config(opts);  // option checks first: they need no handle
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->filterSurfaceArea(curFrame, startFrame, v);
+    BF_CATCH
+}
+int bf_match_filter_dense_verify(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFCachedFrame* frames,
+                                 uint32_t nFrames, uint32_t W, uint32_t H, const float intrinsics[16],
+                                 const BFMatchVerifyOptions* opts) {
+    BF_TRY
+    const MatchVerifyConfig v = make_match_verify_config(opts);
+    check_dense_frame_shape(W, H, intrinsics);
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->filterDenseVerify(curFrame, startFrame, frames, nFrames, W, H, intrinsics, v);
+    BF_CATCH
+}
+int bf_match_verify_stats(bf_matcher* m, uint32_t prev, float area[2], float sums[6]) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->verifyStats(prev, area, sums);
+    BF_CATCH
+}
+int bf_match_and_filter(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFCachedFrame* frames, uint32_t nFrames,
+                        uint32_t W, uint32_t H, const float intrinsics[16], const BFMatchVerifyOptions* opts,
+                        uint32_t* lastMatchedFrame) {
+    BF_TRY
+    const MatchVerifyConfig v = make_match_verify_config(opts);  // every host check before any device work
+    if (frames) check_dense_frame_shape(W, H, intrinsics);
+    BF_REQUIRE(m && lastMatchedFrame, BF_ERR_ARG, "null argument");
+    m->m->checkFrames(curFrame, startFrame);
+    if (frames) m->m->checkDenseShape(nFrames, W, H, intrinsics);
+    m->m->match(curFrame, startFrame);
+    m->m->filter(curFrame, startFrame);
+    m->m->filterSurfaceArea(curFrame, startFrame, v);
+    if (frames) m->m->filterDenseVerify(curFrame, startFrame, frames, nFrames, W, H, intrinsics, v);
+    *lastMatchedFrame = m->m->filterFrames(curFrame, startFrame);
+    BF_CATCH
+}
+int bf_match_debug_set_filtered(bf_matcher* m, uint32_t prev, uint32_t count, const uint32_t* idx) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->debugSetFiltered(prev, count, idx);
     BF_CATCH
 }
 int bf_matcher_synchronize(bf_matcher* m) {

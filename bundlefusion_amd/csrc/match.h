@@ -1,6 +1,7 @@
 // match.h — the sparse matcher (match.hip): image store of key points + descriptors, descriptor matching on
-// the int8 matrix cores, the Kabsch key-point match filter, filterFrames and the EntryJ producer. One handle
-// per Bundler (local / global), everything queued on the handle's stream, no device allocation after the ctor.
+// the int8 matrix cores, the Kabsch key-point match filter, the surface-area and dense-verify filters, filterFrames
+// and the EntryJ producer. One handle per Bundler (local / global), everything queued on the handle's stream, no
+// device allocation after the ctor.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,12 +21,25 @@ struct MatcherConfig {
     float kinv[16] = {};
 };
 
+// thresholds of the surface-area and dense-verify filters (zParametersBundlingDefault.txt / zParametersDefault.txt)
+struct MatchVerifyConfig {
+    float surfAreaPcaThresh = 0.032f;
+    float projCorrDistThres = 0.15f, projCorrNormalThres = 0.97f;
+    float verifySiftErrThresh = 0.075f, verifySiftCorrThresh = 0.02f;
+    float sensorDepthMin = 0.1f, sensorDepthMax = 4.0f;
+};
+
 // BFMatcherOptions -> config with the defaults filled in; throws BF_ERR_ARG on invalid options (host only)
 MatcherConfig make_matcher_config(const BFMatcherOptions* o);
+// ... and BFMatchVerifyOptions (null: every default)
+MatchVerifyConfig make_match_verify_config(const BFMatchVerifyOptions* o);
+// W, H >= 1, W * H <= 2^20, finite intrinsics; throws BF_ERR_ARG (host only)
+void check_dense_frame_shape(uint32_t W, uint32_t H, const float* intrinsics);
 
 class Matcher {
 public:
     static constexpr uint32_t kRaw = BF_MAX_MATCHES_RAW, kFilt = BF_MAX_MATCHES_FILTERED, kDbg = 32;
+    static constexpr uint32_t kSlices = 16;  // row slices (workgroups) per pair of the dense-verify kernel
 
     Matcher(const MatcherConfig& cfg, hipStream_t stream);
     ~Matcher();
@@ -40,6 +54,14 @@ public:
 
     void match(uint32_t cur, uint32_t start);
     void filter(uint32_t cur, uint32_t start);
+    // both reject a pair of the last filter() by setting its filtered count to 0; host checks before any device work
+    void filterSurfaceArea(uint32_t cur, uint32_t start, const MatchVerifyConfig& v);
+    void filterDenseVerify(uint32_t cur, uint32_t start, const BFCachedFrame* frames, uint32_t nFrames, uint32_t W, uint32_t H,
+                           const float* intrinsics, const MatchVerifyConfig& v);
+    void checkFrames(uint32_t cur, uint32_t start) const;
+    void checkDenseShape(uint32_t nFrames, uint32_t W, uint32_t H, const float* intrinsics) const;
+    void verifyStats(uint32_t prev, float* area, float* sums);
+    void debugSetFiltered(uint32_t prev, uint32_t count, const uint32_t* idx);
     uint32_t filterFrames(uint32_t cur, uint32_t start);
     uint32_t addToResiduals(uint32_t cur, uint32_t start, BFEntryJ* out, uint32_t* keyIdx, uint32_t cap, uint32_t* total);
     void rawMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist);
@@ -67,6 +89,9 @@ private:
     DevBuf<float> rawDist_, filtDist_;
     DevBuf<float> T_, Tinv_;                 // [maxImages][16]
     DevBuf<uint32_t> base_;                  // [maxImages] EntryJ base per pair
+    DevBuf<float> area_;                     // [maxImages][2] surface areas of the last filterSurfaceArea (NaN: skipped)
+    DevBuf<float> denseSums_;                // [maxImages][6] {residual, weight, count} x direction (NaN: skipped)
+    DevBuf<float> densePartial_;             // [maxImages][kSlices][6] per-workgroup sums
     DevBuf<uint32_t> dbgSel_;                // rows[32], cols[32]
     DevBuf<int32_t> dbgOut_;                 // dots[32 * 32], rowStats[3 * 32]
     uint32_t* hostTable_ = nullptr;          // pinned, 4 * maxImages

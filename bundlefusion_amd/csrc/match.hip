@@ -1,10 +1,11 @@
-// match.hip — the sparse matcher: descriptor matching + Kabsch filter to EntryJ. Restates the matching side of
-// SIFTImageManager + SiftMatchCU + Bundler::matchAndFilter (paths relative to FriedLiver/Source/):
+// match.hip — the sparse matcher: descriptor matching, the Kabsch, surface-area and dense-verify filters, to EntryJ.
+// Restates the matching side of SIFTImageManager + SiftMatchCU + Bundler::matchAndFilter (paths relative to
+// FriedLiver/Source/):
 //   Bundler.cpp:103-249, SiftGPU/ProgramCU.cu:1634-1936 (MultiplyDescriptor / RowMatch / ColMatch),
-//   SiftGPU/SIFTImageManager.cu:59-314, 610-687, SiftGPU/SIFTImageManager.cpp:44-83, 551-575,
-//   SiftGPU/cuda_kabsch.h:73-229, 281-502.
-// The DoG detector / descriptor, the surface-area and dense-verify filters, tryRevalidation and fuseToGlobal are
-// not here.
+//   SiftGPU/SIFTImageManager.cu:59-607, 610-687, SiftGPU/SIFTImageManager.cpp:44-83, 551-575,
+//   SiftGPU/cuda_kabsch.h:73-229, 281-502, SiftGPU/cuda_surfaceArea.h, SiftGPU/cuda_SVD.h:17-213,
+//   SiftGPU/cuda_EigenValue.h:56-85.
+// The DoG detector / descriptor, tryRevalidation and fuseToGlobal are not here.
 //
 // k_match — one workgroup (4 waves) per image pair (prev, cur), every pair of a call in one launch. The reference
 // writes the num1 x num2 int32 dot matrix to memory and reduces it with two more kernels per pair; here it never
@@ -27,12 +28,15 @@
 //     and keeps an arbitrary 128 of more; the count written is the true number of mutual matches.
 // k_filter — one wave per pair, lane 0 runs filterKeyPointMatches' greedy loop (the reference runs it on one
 // thread too); Kabsch's 3x3 SVD and the covariance eigenvalues use a double-precision Jacobi iteration.
+// k_surface_area — one wave per pair, lanes 0..31 as the reference's warp; k_dense_verify + k_dense_decide — row slices x
+// pairs, sums in a fixed order (the comments at the kernels).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "../../include/bf/bf.h"
+#include "bf_math.h"
 #include "bf_runtime.h"
 #include "match.h"
 
@@ -652,6 +656,332 @@ __global__ __launch_bounds__(32) void k_add_residuals(const BFSiftKeyPoint* keys
     }
 }
 
+// ---- FilterMatchesBySurfaceAreaCU (SIFTImageManager.cu:318-389, cuda_surfaceArea.h) ------------------------------
+// The reference's block is one 32-thread warp, thread t owns match t; here lanes 0..31 of the wave play that warp
+// (lanes 32..63 carry the neutral element), so every sum / min / max is the reference's __shfl_down tree; lane 0's
+// result goes to the whole wave, which keeps control flow uniform.
+__device__ __forceinline__ float tree_sum32(float v) {
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_down(v, off, 32);
+    return __shfl(v, 0);
+}
+__device__ __forceinline__ float tree_min32(float v) {
+    for (int off = 16; off > 0; off >>= 1) v = fminf(v, __shfl_down(v, off, 32));
+    return __shfl(v, 0);
+}
+__device__ __forceinline__ float tree_max32(float v) {
+    for (int off = 16; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 32));
+    return __shfl(v, 0);
+}
+
+// MYEIGEN::jacobi<3> (cuda_SVD.h:138-213), float32: the Numerical-Recipes cyclic sweep (0,1), (0,2), (1,2), threshold
+// 0.2 sm / 9 in sweeps 1-3, at most 50 sweeps. a: upper triangle used; d: eigenvalues; v: rotations accumulated in
+// its COLUMNS. False when 50 sweeps do not converge.
+__device__ bool jacobi3f(float a[3][3], float d[3], float v[3][3]) {
+    float b[3], z[3];
+    for (int ip = 0; ip < 3; ip++) {
+        for (int iq = 0; iq < 3; iq++) v[ip][iq] = 0.0f;
+        v[ip][ip] = 1.0f;
+    }
+    for (int ip = 0; ip < 3; ip++) {
+        b[ip] = d[ip] = a[ip][ip];
+        z[ip] = 0.0f;
+    }
+    for (int i = 1; i <= 50; i++) {
+        const float sm = (fabsf(a[0][1]) + fabsf(a[0][2])) + fabsf(a[1][2]);
+        if (sm == 0.0f) return true;
+        const float tresh = i < 4 ? 0.2f * sm / 9.0f : 0.0f;
+#pragma unroll
+        for (int pq = 0; pq < 3; pq++) {
+            const int ip = pq == 2 ? 1 : 0, iq = pq == 0 ? 1 : 2;
+            const float g = 100.0f * fabsf(a[ip][iq]);
+            if (i > 4 && fabsf(d[ip]) + g == fabsf(d[ip]) && fabsf(d[iq]) + g == fabsf(d[iq])) {
+                a[ip][iq] = 0.0f;
+            } else if (fabsf(a[ip][iq]) > tresh) {
+                float h = d[iq] - d[ip], t;
+                if (fabsf(h) + g == fabsf(h)) {
+                    t = a[ip][iq] / h;
+                } else {
+                    const float theta = 0.5f * h / a[ip][iq];
+                    t = 1.0f / (fabsf(theta) + sqrtf(1.0f + theta * theta));
+                    if (theta < 0.0f) t = -t;
+                }
+                const float c = 1.0f / sqrtf(1.0f + t * t), s = t * c, tau = s / (1.0f + c);
+                h = t * a[ip][iq];
+                z[ip] -= h;
+                z[iq] += h;
+                d[ip] -= h;
+                d[iq] += h;
+                a[ip][iq] = 0.0f;
+                // ROTATE(a, i, j, k, l): g = a[i][j], h = a[k][l]; a[i][j] = g - s (h + g tau); a[k][l] = h + s (g - h tau)
+                const int j = 3 - ip - iq;  // the one remaining index of a 3x3
+                {
+                    float* x = j < ip ? &a[j][ip] : &a[ip][j];
+                    float* y = j < iq ? &a[j][iq] : &a[iq][j];
+                    const float gg = *x, hh = *y;
+                    *x = gg - s * (hh + gg * tau);
+                    *y = hh + s * (gg - hh * tau);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const float gg = v[k][ip], hh = v[k][iq];
+                    v[k][ip] = gg - s * (hh + gg * tau);
+                    v[k][iq] = hh + s * (gg - hh * tau);
+                }
+            }
+        }
+        for (int ip = 0; ip < 3; ip++) {
+            b[ip] += z[ip];
+            d[ip] = b[ip];
+            z[ip] = 0.0f;
+        }
+    }
+    return false;
+}
+
+// MYEIGEN::eigenSystem (cuda_SVD.h:69-125): ev[i] = ROW i of the rotation matrix (:95-100), although jacobi leaves
+// the eigenvectors in its columns; then a selection sort by |eigenvalue| descending that moves those rows along.
+// Restated as the reference computes it: s_surfAreaPcaThresh was tuned against this.
+__device__ bool eigen_system3(const float V[3][3], float ev[3][3]) {
+    float a[3][3], d[3], v[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) a[i][j] = V[j][i];
+    if (!jacobi3f(a, d, v)) return false;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) ev[i][j] = v[i][j];
+    for (int i = 0; i < 3; i++) {
+        float curMax = 0.0f;
+        int at = -1;
+        for (int j = i; j < 3; j++)
+            if (fabsf(d[j]) > curMax) {
+                curMax = fabsf(d[j]);
+                at = j;
+            }
+        if (at != i && at != -1) {
+            float t = d[i]; d[i] = d[at]; d[at] = t;
+            for (int j = 0; j < 3; j++) {
+                t = ev[i][j]; ev[i][j] = ev[at][j]; ev[at][j] = t;
+            }
+        }
+    }
+    return true;
+}
+
+// area of one side of a pair (which = 0 prev, 1 cur); every lane returns the same value
+__device__ float surface_area_side(const BFSiftKeyPoint* keys, const uint2* idx, uint32_t n, const float* kinv, uint32_t which,
+                                   uint32_t lane) {
+    const bool mine = lane < n;
+    float pt[3] = {0.0f, 0.0f, 0.0f};
+    if (mine) {
+        const uint2 ij = idx[lane];
+        key_point(kinv, keys[which ? ij.y : ij.x], pt);
+    }
+    // computeKeyPointMatchesCovariance
+    float mean[3], V[3][3];
+    for (int r = 0; r < 3; r++) mean[r] = tree_sum32(pt[r]) / (float)n;
+    const float dl[3] = {pt[0] - mean[0], pt[1] - mean[1], pt[2] - mean[2]};
+    for (int r = 0; r < 3; r++)
+        for (int c = r; c < 3; c++) V[r][c] = V[c][r] = tree_sum32(mine ? dl[r] * dl[c] : 0.0f) / (float)n;
+    float ev[3][3];
+    if (!eigen_system3(V, ev)) return 0.0f;
+    // projectKeysToPlane: onto the plane through the mean orthogonal to ev[2], in the (ev[0], ev[1]) frame
+    float px = 0.0f, py = 0.0f;
+    if (mine) {
+        const float k = (ev[2][0] * dl[0] + ev[2][1] * dl[1]) + ev[2][2] * dl[2];
+        const float s[3] = {(pt[0] - k * ev[2][0]) - mean[0], (pt[1] - k * ev[2][1]) - mean[1], (pt[2] - k * ev[2][2]) - mean[2]};
+        px = (s[0] * ev[0][0] + s[1] * ev[0][1]) + s[2] * ev[0][2];
+        py = (s[0] * ev[1][0] + s[1] * ev[1][1]) + s[2] * ev[1][2];
+    }
+    // computeAreaOrientedBoundingBox2: computeCovariance2d, computeEigenValues / computeEigenVector (2x2)
+    const float mx = tree_sum32(px) / (float)n, my = tree_sum32(py) / (float)n;
+    const float ex = px - mx, ey = py - my;
+    const float cxx = tree_sum32(mine ? ex * ex : 0.0f) / (float)n, cxy = tree_sum32(mine ? ex * ey : 0.0f) / (float)n,
+                cyy = tree_sum32(mine ? ey * ey : 0.0f) / (float)n;
+    const float disc = 0.5f * sqrtf((cxx - cyy) * (cxx - cyy) + 4.0f * cxy * cxy);
+    const float lam[2] = {(cxx + cyy) / 2.0f + disc, (cxx + cyy) / 2.0f - disc};
+    float ax[2][2];
+    for (int k = 0; k < 2; k++) {
+        float vx = -cxy, vy = cxx - lam[k];
+        const float mag = sqrtf(vx * vx + vy * vy);
+        vx /= mag;
+        vy /= mag;
+        const float inv = 1.0f / sqrtf(vx * vx + vy * vy);  // normalize(): v * rsqrtf(dot(v, v))
+        ax[k][0] = vx * inv;
+        ax[k][1] = vy * inv;
+    }
+    const float qx = ax[0][0] * px + ax[0][1] * py, qy = ax[1][0] * px + ax[1][1] * py;
+    const float minX = tree_min32(mine ? qx : 3.402823466e+38f), minY = tree_min32(mine ? qy : 3.402823466e+38f);
+    const float maxX = tree_max32(mine ? qx : -3.402823466e+38f), maxY = tree_max32(mine ? qy : -3.402823466e+38f);
+    const float extX = maxX - minX, extY = maxY - minY;
+    if (extX < 0.00001f || extY < 0.00001f) return 0.0f;
+    return extX * extY;
+}
+
+__global__ __launch_bounds__(64) void k_surface_area(const BFSiftKeyPoint* keys, uint32_t* filtCount, const uint2* filtIdx,
+                                                     const uint32_t* table, const float* kinvDev, float* area, uint32_t cur,
+                                                     uint32_t start, float areaThresh) {
+    const uint32_t prev = start + blockIdx.x;
+    if (prev == cur) return;
+    const uint32_t n = min(filtCount[prev], FILT);
+    if (n == 0) return;
+    if (!table[4 * prev + 2]) return;
+    float kinv[16];
+    for (int k = 0; k < 16; k++) kinv[k] = kinvDev[k];
+    const uint32_t lane = threadIdx.x;
+    const uint2* idx = filtIdx + (size_t)prev * FILT;
+    const float a0 = surface_area_side(keys, idx, n, kinv, 0, lane);
+    const float a1 = surface_area_side(keys, idx, n, kinv, 1, lane);
+    if (lane == 0) {
+        area[2 * (size_t)prev] = a0;
+        area[2 * (size_t)prev + 1] = a1;
+        if (a0 < areaThresh && a1 < areaThresh) filtCount[prev] = 0;
+    }
+}
+
+// ---- FilterMatchesByDenseVerifyCU (SIFTImageManager.cu:417-607) ----------------------------------------------
+// The reference runs one block of W x ceil(H / 32) threads per pair, which caps W ceil(H / 32) at 1 024 and leaves a
+// local matcher's <= 10 pairs on 10 CUs. Here a pair's rows are cut into DV_SLICES slices, one 256-thread workgroup
+// each (grid = slices x pairs); a thread takes pixels t, t + 256, ... of its slice, both directions of a pixel as the
+// reference's thread does, two pixels at a time so that four gathers are in flight before the first is used. Sums:
+// per thread in pixel order, per direction; the __shfl_down tree per wave; waves 0..3; k_dense_decide then adds the
+// slices 0, 1, ... in order. The reference adds warp sums with shared-memory float atomics in race order: this
+// fixed order is the stage's one deliberate departure, results are bit-deterministic.
+constexpr uint32_t DV_SLICES = Matcher::kSlices, DV_WG = 256, DV_UNROLL = 2;
+
+struct DenseArgs {
+    const BFCachedFrame* frames;
+    uint32_t* filtCount;
+    const float* T;
+    const float* Tinv;
+    const uint32_t* table;
+    float* partial;  // [maxImages][DV_SLICES][6]
+    float* sums;     // [maxImages][6]
+    uint32_t cur, start, n, W, H, rowsPerSlice, nSlices;
+    float K[16];
+    float distT, normT, errT, corrT, dmin, dmax;
+};
+
+struct DenseProbe {
+    float4 pT;
+    float nx, ny, nz;
+    uint32_t t;  // target pixel (0 when !ok: any frame has pixel 0)
+    bool ok;
+};
+
+// computeProjError up to the bounds test (SIFTImageManager.cu:433-451)
+__device__ __forceinline__ DenseProbe dense_probe(const DenseArgs& A, const float* tr, float4 pIn, float4 nIn, float dIn, bool live) {
+    DenseProbe P;
+    P.t = 0;
+    P.ok = false;
+    nIn.w = 0.0f;
+    P.pT = make_float4(tr[0] * pIn.x + tr[1] * pIn.y + tr[2] * pIn.z + tr[3] * pIn.w, tr[4] * pIn.x + tr[5] * pIn.y + tr[6] * pIn.z + tr[7] * pIn.w,
+                       tr[8] * pIn.x + tr[9] * pIn.y + tr[10] * pIn.z + tr[11] * pIn.w,
+                       tr[12] * pIn.x + tr[13] * pIn.y + tr[14] * pIn.z + tr[15] * pIn.w);
+    P.nx = tr[0] * nIn.x + tr[1] * nIn.y + tr[2] * nIn.z + tr[3] * nIn.w;
+    P.ny = tr[4] * nIn.x + tr[5] * nIn.y + tr[6] * nIn.z + tr[7] * nIn.w;
+    P.nz = tr[8] * nIn.x + tr[9] * nIn.y + tr[10] * nIn.z + tr[11] * nIn.w;
+    if (!(live && pIn.x != -INFINITY && nIn.x != -INFINITY && dIn >= A.dmin && dIn <= A.dmax)) return P;
+    const float* K = A.K;
+    const float qx = K[0] * P.pT.x + K[1] * P.pT.y + K[2] * P.pT.z + K[3] * 1.0f;
+    const float qy = K[4] * P.pT.x + K[5] * P.pT.y + K[6] * P.pT.z + K[7] * 1.0f;
+    const float qz = K[8] * P.pT.x + K[9] * P.pT.y + K[10] * P.pT.z + K[11] * 1.0f;
+    const int sx = f2i(roundf(qx / qz)), sy = f2i(roundf(qy / qz));
+    if (!(sx >= 0 && sy >= 0 && sx < (int)A.W && sy < (int)A.H)) return P;  // the gather below is inside the image
+    P.t = (uint32_t)sy * A.W + (uint32_t)sx;
+    P.ok = true;
+    return P;
+}
+
+// ... and from the gathered target on (:452-486): (residual, weight, 1) is added to s[0..2]
+__device__ __forceinline__ void dense_accept(const DenseArgs& A, const DenseProbe& P, float4 pTg, float4 nTg, float tgtDepth, float* s) {
+    if (!(P.ok && pTg.x != -INFINITY && nTg.x != -INFINITY)) return;
+    const float dx = P.pT.x - pTg.x, dy = P.pT.y - pTg.y, dz = P.pT.z - pTg.z, dw = P.pT.w - pTg.w;
+    const float d = sqrtf(dx * dx + dy * dy + dz * dz + dw * dw);  // length(float4)
+    const float dN = P.nx * nTg.x + P.ny * nTg.y + P.nz * nTg.z;
+    if (!(tgtDepth >= A.dmin && tgtDepth <= A.dmax)) return;
+    const bool bad = (tgtDepth != -INFINITY && P.pT.z < tgtDepth) && d > A.distT;  // known bad match
+    if (!((dN >= A.normT && d <= A.distT) || bad)) return;
+    const float camZ = (P.pT.z - A.dmin) / (A.dmax - A.dmin);
+    const float w = fmaxf(0.0f, 0.5f * ((1.0f - d / A.distT) + (1.0f - camZ)));
+    s[0] += d;
+    s[1] += w;
+    s[2] += 1.0f;
+}
+
+__global__ __launch_bounds__(DV_WG) void k_dense_verify(DenseArgs A) {
+    __shared__ float sh[6][DV_WG / 64];
+    const uint32_t prev = A.start + blockIdx.y, slice = blockIdx.x;
+    if (prev == A.cur) return;
+    if (A.filtCount[prev] == 0) return;
+    if (!A.table[4 * prev + 2]) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row0 = slice * A.rowsPerSlice, row1 = min(A.H, row0 + A.rowsPerSlice);  // row0 < H: nSlices slices
+    const uint32_t first = row0 * A.W, npix = (row1 - row0) * A.W;
+    float T[16], Ti[16];
+    for (int k = 0; k < 16; k++) {
+        T[k] = A.T[16 * (size_t)prev + k];
+        Ti[k] = A.Tinv[16 * (size_t)prev + k];
+    }
+    const BFCachedFrame fp = A.frames[prev], fc = A.frames[A.cur];
+    if (!fp.depth || !fp.campos || !fp.normals || !fc.depth || !fc.campos || !fc.normals) {  // no frame: no correspondence
+        if (tid < 6) A.partial[((size_t)prev * DV_SLICES + slice) * 6 + tid] = 0.0f;
+        return;
+    }
+    const float4* pos[2] = {(const float4*)fp.campos, (const float4*)fc.campos};
+    const float4* nrm[2] = {(const float4*)fp.normals, (const float4*)fc.normals};
+    const float* dep[2] = {fp.depth, fc.depth};
+    float s[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    for (uint32_t p0 = tid; p0 < npix; p0 += DV_WG * DV_UNROLL) {
+        DenseProbe P[DV_UNROLL][2];
+#pragma unroll
+        for (uint32_t u = 0; u < DV_UNROLL; u++) {
+            const uint32_t p = p0 + u * DV_WG;
+            const bool live = p < npix;
+            const uint32_t idx = first + (live ? p : 0u);
+#pragma unroll
+            for (int dir = 0; dir < 2; dir++)  // 0: prev's pixel into cur by T; 1: cur's pixel into prev by Tinv
+                P[u][dir] = dense_probe(A, dir ? Ti : T, pos[dir][idx], nrm[dir][idx], dep[dir][idx], live);
+        }
+        float4 gp[DV_UNROLL][2], gn[DV_UNROLL][2];
+        float gd[DV_UNROLL][2];
+#pragma unroll
+        for (uint32_t u = 0; u < DV_UNROLL; u++)
+#pragma unroll
+            for (int dir = 0; dir < 2; dir++) {
+                const uint32_t t = P[u][dir].t;
+                gp[u][dir] = pos[1 - dir][t];
+                gn[u][dir] = nrm[1 - dir][t];
+                gd[u][dir] = dep[1 - dir][t];
+            }
+#pragma unroll
+        for (uint32_t u = 0; u < DV_UNROLL; u++)
+#pragma unroll
+            for (int dir = 0; dir < 2; dir++) dense_accept(A, P[u][dir], gp[u][dir], gn[u][dir], gd[u][dir], s[dir]);
+    }
+    float v[6] = {s[0][0], s[0][1], s[0][2], s[1][0], s[1][1], s[1][2]};
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < 6; q++) v[q] += __shfl_down(v[q], off);
+    if ((tid & 63) == 0)
+        for (int q = 0; q < 6; q++) sh[q][tid >> 6] = v[q];
+    __syncthreads();
+    if (tid < 6) A.partial[((size_t)prev * DV_SLICES + slice) * 6 + tid] = ((sh[tid][0] + sh[tid][1]) + sh[tid][2]) + sh[tid][3];
+}
+
+// one thread per pair: slices in order, then the reference's verdict (SIFTImageManager.cu:572-584)
+__global__ __launch_bounds__(64) void k_dense_decide(DenseArgs A) {
+    const uint32_t prev = A.start + blockIdx.x * 64 + threadIdx.x;
+    if (prev >= A.n || prev == A.cur) return;
+    if (A.filtCount[prev] == 0) return;
+    if (!A.table[4 * prev + 2]) return;
+    float s[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t sl = 0; sl < A.nSlices; sl++)
+        for (int q = 0; q < 6; q++) s[q] += A.partial[((size_t)prev * DV_SLICES + sl) * 6 + q];
+    for (int q = 0; q < 6; q++) A.sums[6 * (size_t)prev + q] = s[q];
+    const float err = (s[0] + s[3]) / (s[1] + s[4]);
+    const float corr = 0.5f * (s[2] + s[5]) / (float)(A.W * A.H);
+    if (corr < A.corrT || err > A.errT || isnan(err)) A.filtCount[prev] = 0;
+}
+
 }  // namespace
 
 MatcherConfig make_matcher_config(const BFMatcherOptions* o) {
@@ -697,6 +1027,9 @@ Matcher::Matcher(const MatcherConfig& cfg, hipStream_t stream) : cfg_(cfg), stre
     base_.alloc(n + 16);  // + intrinsicsInv (16 floats) behind the bases
     dbgSel_.alloc(2 * kDbg);
     dbgOut_.alloc(kDbg * kDbg + 3 * kDbg);
+    area_.alloc(2 * n);
+    denseSums_.alloc(6 * n);
+    densePartial_.alloc(6 * n * kSlices);
     BF_HIP(hipHostMalloc((void**)&hostTable_, 4 * n * sizeof(uint32_t), hipHostMallocDefault));
     BF_HIP(hipHostMalloc((void**)&hostCounts_, n * sizeof(uint32_t), hipHostMallocDefault));
     BF_HIP(hipHostMalloc((void**)&hostBase_, (n + 16) * sizeof(uint32_t), hipHostMallocDefault));
@@ -728,6 +1061,8 @@ void Matcher::reset() {
     BF_HIP(hipMemsetAsync(filtDist_.p, 0, filtDist_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(T_.p, 0, T_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(Tinv_.p, 0, Tinv_.bytes(), stream_));
+    BF_HIP(hipMemsetAsync(area_.p, 0xFF, area_.bytes(), stream_));  // NaN: no stage has looked at the pair
+    BF_HIP(hipMemsetAsync(denseSums_.p, 0xFF, denseSums_.bytes(), stream_));
 }
 
 uint32_t Matcher::addImage(const BFSiftKeyPoint* keys, const uint8_t* descs, uint32_t n) {
@@ -865,6 +1200,106 @@ uint32_t Matcher::addToResiduals(uint32_t cur, uint32_t start, BFEntryJ* out, ui
         BF_HIP(hipStreamSynchronize(stream_));
     }
     return sum < cap ? sum : cap;
+}
+
+MatchVerifyConfig make_match_verify_config(const BFMatchVerifyOptions* o) {
+    MatchVerifyConfig c;
+    if (!o) return c;
+    const float v[7] = {o->surfAreaPcaThresh, o->projCorrDistThres, o->projCorrNormalThres, o->verifySiftErrThresh,
+                        o->verifySiftCorrThresh, o->sensorDepthMin, o->sensorDepthMax};
+    for (float x : v) BF_REQUIRE(std::isfinite(x) && x >= 0.0f, BF_ERR_ARG, "match verify options: non-finite or negative threshold");
+    if (o->surfAreaPcaThresh > 0.0f) c.surfAreaPcaThresh = o->surfAreaPcaThresh;
+    if (o->projCorrDistThres > 0.0f) c.projCorrDistThres = o->projCorrDistThres;
+    if (o->projCorrNormalThres > 0.0f) c.projCorrNormalThres = o->projCorrNormalThres;
+    if (o->verifySiftErrThresh > 0.0f) c.verifySiftErrThresh = o->verifySiftErrThresh;
+    if (o->verifySiftCorrThresh > 0.0f) c.verifySiftCorrThresh = o->verifySiftCorrThresh;
+    if (o->sensorDepthMin > 0.0f) c.sensorDepthMin = o->sensorDepthMin;
+    if (o->sensorDepthMax > 0.0f) c.sensorDepthMax = o->sensorDepthMax;
+    BF_REQUIRE(c.sensorDepthMax > c.sensorDepthMin, BF_ERR_ARG, "match verify options: sensorDepthMax <= sensorDepthMin");
+    return c;
+}
+
+void Matcher::checkFrames(uint32_t cur, uint32_t start) const {
+    const uint32_t n = numImages();
+    BF_REQUIRE(cur < n, BF_ERR_ARG, "curFrame >= numImages");
+    BF_REQUIRE(start <= n, BF_ERR_ARG, "startFrame > numImages");
+}
+
+void check_dense_frame_shape(uint32_t W, uint32_t H, const float* intrinsics) {
+    BF_REQUIRE(W >= 1 && H >= 1 && (uint64_t)W * H <= (1ull << 20), BF_ERR_ARG, "cache frame size: W, H >= 1 and W * H <= 2^20");
+    BF_REQUIRE(intrinsics != nullptr, BF_ERR_ARG, "null intrinsics");
+    for (int k = 0; k < 16; k++) BF_REQUIRE(std::isfinite(intrinsics[k]), BF_ERR_ARG, "non-finite cache intrinsics");
+}
+
+void Matcher::checkDenseShape(uint32_t nFrames, uint32_t W, uint32_t H, const float* intrinsics) const {
+    check_dense_frame_shape(W, H, intrinsics);
+    BF_REQUIRE(nFrames >= numImages(), BF_ERR_ARG, "nFrames below the matcher's image count");
+}
+
+void Matcher::filterSurfaceArea(uint32_t cur, uint32_t start, const MatchVerifyConfig& v) {
+    checkFrames(cur, start);
+    const uint32_t n = numImages();
+    BF_HIP(hipMemsetAsync(area_.p, 0xFF, area_.bytes(), stream_));
+    if (start == n) return;
+    uploadTable();
+    k_surface_area<<<n - start, 64, 0, stream_>>>(keys_.p, filtCount_.p, filtIdx_.p, table_.p, (const float*)(base_.p + cfg_.maxImages),
+                                                  area_.p, cur, start, v.surfAreaPcaThresh);
+    BF_LAUNCH_CHECK();
+}
+
+void Matcher::filterDenseVerify(uint32_t cur, uint32_t start, const BFCachedFrame* frames, uint32_t nFrames, uint32_t W, uint32_t H,
+                                const float* intrinsics, const MatchVerifyConfig& v) {
+    checkFrames(cur, start);
+    checkDenseShape(nFrames, W, H, intrinsics);
+    BF_REQUIRE(frames != nullptr, BF_ERR_ARG, "null cache frames");
+    const uint32_t n = numImages();
+    BF_HIP(hipMemsetAsync(denseSums_.p, 0xFF, denseSums_.bytes(), stream_));
+    if (start == n) return;
+    uploadTable();
+    DenseArgs A{};
+    A.frames = frames;
+    A.filtCount = filtCount_.p;
+    A.T = T_.p;
+    A.Tinv = Tinv_.p;
+    A.table = table_.p;
+    A.partial = densePartial_.p;
+    A.sums = denseSums_.p;
+    A.cur = cur;
+    A.start = start;
+    A.n = n;
+    A.W = W;
+    A.H = H;
+    A.rowsPerSlice = div_up(H, DV_SLICES);
+    A.nSlices = div_up(H, A.rowsPerSlice);  // <= DV_SLICES, every slice has a row
+    for (int k = 0; k < 16; k++) A.K[k] = intrinsics[k];
+    A.distT = v.projCorrDistThres;
+    A.normT = v.projCorrNormalThres;
+    A.errT = v.verifySiftErrThresh;
+    A.corrT = v.verifySiftCorrThresh;
+    A.dmin = v.sensorDepthMin;
+    A.dmax = v.sensorDepthMax;
+    k_dense_verify<<<dim3(A.nSlices, n - start), DV_WG, 0, stream_>>>(A);
+    BF_LAUNCH_CHECK();
+    k_dense_decide<<<div_up(n - start, 64u), 64, 0, stream_>>>(A);
+    BF_LAUNCH_CHECK();
+}
+
+void Matcher::verifyStats(uint32_t prev, float* area, float* sums) {
+    BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
+    BF_HIP(hipStreamSynchronize(stream_));
+    if (area) BF_HIP(hipMemcpy(area, area_.p + 2 * (size_t)prev, 8, hipMemcpyDeviceToHost));
+    if (sums) BF_HIP(hipMemcpy(sums, denseSums_.p + 6 * (size_t)prev, 24, hipMemcpyDeviceToHost));
+}
+
+void Matcher::debugSetFiltered(uint32_t prev, uint32_t count, const uint32_t* idx) {
+    BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
+    BF_REQUIRE(count <= kFilt && (idx || count == 0), BF_ERR_ARG, "at most 25 filtered matches");
+    for (uint32_t k = 0; k < 2 * count; k++) BF_REQUIRE(idx[k] < totalKeys_, BF_ERR_ARG, "key index >= the store's key count");
+    uint32_t list[2 * kFilt];
+    for (uint32_t k = 0; k < 2 * kFilt; k++) list[k] = k < 2 * count ? idx[k] : 0xFFFFFFFFu;
+    BF_HIP(hipStreamSynchronize(stream_));
+    BF_HIP(hipMemcpy(filtIdx_.p + (size_t)prev * kFilt, list, sizeof(list), hipMemcpyHostToDevice));
+    BF_HIP(hipMemcpy(filtCount_.p + prev, &count, 4, hipMemcpyHostToDevice));
 }
 
 void Matcher::rawMatches(uint32_t prev, uint32_t* count, uint32_t* idx, float* dist) {

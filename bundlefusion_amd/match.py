@@ -1,5 +1,6 @@
 """Python binding of the sparse matcher (bf_matcher_*): the matching side of SIFTImageManager + SiftMatchCU +
-Bundler::matchAndFilter. Key points and 128-byte descriptors in, EntryJ and pair transforms out."""
+Bundler::matchAndFilter, with its Kabsch, surface-area and dense-verify filters. Key points and 128-byte descriptors in,
+EntryJ and pair transforms out."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,7 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import DeviceArray, check, lib
-from .abi import (ENTRYJ_DTYPE, MAX_MATCHES_FILTERED, MAX_MATCHES_RAW, SIFT_KEYPOINT_DTYPE, BFMatcherOptions)
+from .abi import (ENTRYJ_DTYPE, MAX_MATCHES_FILTERED, MAX_MATCHES_RAW, SIFT_KEYPOINT_DTYPE, BFCachedFrame, BFMatcherOptions,
+                  BFMatchVerifyOptions)
 
 NO_FRAME = 0xFFFFFFFF
 
@@ -21,6 +23,52 @@ def matcher_options(max_images: int, max_keys_per_image: int = 1024, intrinsics_
     k = np.eye(4, dtype=np.float32) if intrinsics_inv is None else np.asarray(intrinsics_inv, np.float32).reshape(4, 4)
     o.intrinsicsInv[:] = k.ravel().tolist()
     return o
+
+
+def match_verify_options(surf_area_pca_thresh=0.032, proj_corr_dist_thres=0.15, proj_corr_normal_thres=0.97,
+                         verify_sift_err_thresh=0.075, verify_sift_corr_thresh=0.02, sensor_depth_min=0.1,
+                         sensor_depth_max=4.0) -> BFMatchVerifyOptions:
+    """Thresholds of the surface-area and dense-verify filters; the defaults are zParametersBundlingDefault.txt's and
+    zParametersDefault.txt's (a field set to 0 takes its default too)."""
+    o = BFMatchVerifyOptions()
+    o.surfAreaPcaThresh, o.projCorrDistThres, o.projCorrNormalThres = surf_area_pca_thresh, proj_corr_dist_thres, proj_corr_normal_thres
+    o.verifySiftErrThresh, o.verifySiftCorrThresh = verify_sift_err_thresh, verify_sift_corr_thresh
+    o.sensorDepthMin, o.sensorDepthMax = sensor_depth_min, sensor_depth_max
+    return o
+
+
+class CacheFrames:
+    """Device BFCachedFrame[n] table for filter_dense_verify / match_and_filter, with the frame size and the row-major
+    4x4 intrinsics of the frames. `table` keeps the device array alive; `keep` whatever owns the frames' memory."""
+
+    def __init__(self, frames, width: int, height: int, intrinsics, keep=None):
+        frames = list(frames)
+        tab = (BFCachedFrame * max(len(frames), 1))(*frames)
+        self.table = DeviceArray.from_host(np.frombuffer(bytes(tab), np.uint8).copy())
+        self.n, self.width, self.height = len(frames), int(width), int(height)
+        self.intrinsics = np.ascontiguousarray(np.asarray(intrinsics, np.float32).reshape(16))
+        self.keep = keep
+
+    @classmethod
+    def from_cache(cls, cache, n: int | None = None) -> "CacheFrames":
+        """The first n frames (default: all) of a CUDACache; the cache is synchronised, so the frames are complete."""
+        n = cache.getNumFrames() if n is None else n
+        cache.synchronize()
+        return cls([cache.frame(i) for i in range(n)], cache.opts.width, cache.opts.height, cache.intrinsics()[0], keep=cache)
+
+    @classmethod
+    def from_host(cls, frames, intrinsics) -> "CacheFrames":
+        """frames: dicts of host arrays depth [H, W], campos [H, W, 4], normals [H, W, 4] (float32), uploaded."""
+        keep, tab = [], []
+        H, W = np.asarray(frames[0]["depth"]).shape
+        for f in frames:
+            c = BFCachedFrame()
+            for name in ("depth", "campos", "normals"):
+                d = DeviceArray.from_host(np.ascontiguousarray(f[name], np.float32))
+                keep.append(d)
+                setattr(c, name, d.ptr.value)
+            tab.append(c)
+        return cls(tab, W, H, intrinsics, keep=keep)
 
 
 class Matcher:
@@ -95,13 +143,48 @@ class Matcher:
         check(lib().bf_matcher_filter_frames(self.h, C.c_uint32(cur), C.c_uint32(start), C.byref(last)))
         return last.value
 
-    def match_and_filter(self, cur: int, start: int | None = None) -> int:
-        """Bundler::matchAndFilter up to filterFrames; returns lastMatchedFrame (NO_FRAME if none)."""
+    def _verify(self, verify):
+        return C.byref(verify) if verify is not None else None
+
+    def filter_surface_area(self, cur: int, start: int = 0, verify: BFMatchVerifyOptions | None = None):
+        check(lib().bf_match_filter_surface_area(self.h, C.c_uint32(cur), C.c_uint32(start), self._verify(verify)))
+
+    def filter_dense_verify(self, cur: int, start: int, cache: CacheFrames, verify: BFMatchVerifyOptions | None = None):
+        check(lib().bf_match_filter_dense_verify(self.h, C.c_uint32(cur), C.c_uint32(start), cache.table.ptr, C.c_uint32(cache.n),
+                                                 C.c_uint32(cache.width), C.c_uint32(cache.height),
+                                                 cache.intrinsics.ctypes.data_as(C.c_void_p), self._verify(verify)))
+
+    def verify_stats(self, prev: int):
+        """(area [2] = prev's side, cur's side; sums [2, 3] = {sumResidual, sumWeight, numCorr} of prev -> cur and of
+        cur -> prev) as the last filter_surface_area / filter_dense_verify left them; NaN where a stage skipped the pair."""
+        area, sums = np.empty(2, np.float32), np.empty(6, np.float32)
+        check(lib().bf_match_verify_stats(self.h, C.c_uint32(prev), area.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
+        return area, sums.reshape(2, 3)
+
+    def debug_set_filtered(self, prev: int, idx):
+        """Test hook: replace pair prev's filtered list by idx [n <= 25, 2] (indices into the linear key array)."""
+        idx = np.ascontiguousarray(idx, np.uint32).reshape(-1, 2)
+        check(lib().bf_match_debug_set_filtered(self.h, C.c_uint32(prev), C.c_uint32(len(idx)), idx.ctypes.data_as(C.c_void_p)))
+
+    def match_and_filter(self, cur: int, start: int | None = None, cache: CacheFrames | None = None,
+                         verify: BFMatchVerifyOptions | None = None) -> int:
+        """Bundler::matchAndFilter up to filterFrames; returns lastMatchedFrame (NO_FRAME if none). Without `cache` and
+        `verify`: match, Kabsch filter, filterFrames. With either, the reference's whole chain in one library call:
+        the surface-area filter too, and the dense verify when `cache` is given."""
         if start is None:
             start = 0 if self.num_images() == cur + 1 else cur + 1
-        self.match(cur, start)
-        self.filter(cur, start)
-        return self.filter_frames(cur, start)
+        if cache is None and verify is None:
+            self.match(cur, start)
+            self.filter(cur, start)
+            return self.filter_frames(cur, start)
+        last = C.c_uint32()
+        K = cache.intrinsics.ctypes.data_as(C.c_void_p) if cache is not None else None
+        check(lib().bf_match_and_filter(self.h, C.c_uint32(cur), C.c_uint32(start), cache.table.ptr if cache is not None else None,
+                                        C.c_uint32(cache.n if cache is not None else 0),
+                                        C.c_uint32(cache.width if cache is not None else 0),
+                                        C.c_uint32(cache.height if cache is not None else 0), K, self._verify(verify),
+                                        C.byref(last)))
+        return last.value
 
     def add_to_residuals(self, cur: int, start: int, cap: int, out: DeviceArray | None = None, want_key_indices=False):
         """(host EntryJ array, total found[, key index pairs [n, 2]])."""

@@ -29,7 +29,8 @@ extern "C" {
                              splatRowCap, BFReconOptions.bundlingPriority, bf_set_host_threads; no environment switches),
                              BFSceneCapacity + bf_scene_capacity / bf_recon_scene_capacity (scene errors fail the loop),
                              bf_recon_set_render (visualizeFrame's render per frame);
-                             additive, still 4: the sparse matcher (BFSiftKeyPoint, BFMatcherOptions, bf_matcher_*) */
+                             additive, still 4: the sparse matcher (BFSiftKeyPoint, BFMatcherOptions, bf_matcher_*);
+                             additive, still 4: its surface-area and dense-verify filters (BFMatchVerifyOptions, bf_match_*) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -603,8 +604,9 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
                        uint32_t* total);
 
 /* ---- sparse matcher: the matching side of SIFTImageManager + SiftMatch + Bundler::matchAndFilter ----------
- * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out (the DoG detector /
- * descriptor, the surface-area and dense-verify filters, tryRevalidation and fuseToGlobal are not part of it).
+ * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out, through the reference's whole
+ * filter chain: Kabsch, surface area, dense verify, filterFrames (the DoG detector / descriptor, tryRevalidation and
+ * fuseToGlobal are not part of it).
  * Work is queued on the matcher's own stream; the read-backs and bf_matcher_filter_frames / _add_to_residuals
  * wait for it. No device allocation after bf_matcher_create. Per-pair results are indexed by the earlier image
  * `prev`, as the reference's d_curr* arrays are, and hold the last bf_matcher_match / _filter.
@@ -614,7 +616,13 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
  * 128 survive. Here a pair's raw list is ordered by (dot product descending, current key index ascending) -
  * distance ascending - and the first 128 of that order are kept, so results are bit-deterministic; the raw count
  * reported is the true number of mutual matches (it may exceed 128). bf_matcher_add_to_residuals likewise writes
- * pairs in ascending prev order instead of at an atomic base pointer. */
+ * pairs in ascending prev order instead of at an atomic base pointer.
+ *
+ * A second one, in bf_match_filter_dense_verify: the reference adds its warps' partial sums of a pair with shared-memory
+ * float atomicAdd, in race order. Here they are added in a fixed order (pixels per thread, a wave tree, the waves, the
+ * row slices), so the sums and the verdicts that hinge on them are bit-deterministic.
+ *
+ * The entries added for the two filters are spelled bf_match_*: they take the same bf_matcher handle. */
 typedef struct bf_matcher bf_matcher;
 /* SIFTImageManager ctor (SIFTImageManager.cpp:44-83): capacity maxImages x maxKeysPerImage */
 int bf_matcher_create(const BFMatcherOptions* opts, bf_matcher** out);
@@ -666,6 +674,38 @@ int bf_matcher_transforms(bf_matcher* m, uint32_t prev, float T[16], float Tinv[
  * bf_matcher_match would. */
 int bf_matcher_debug_dots(bf_matcher* m, uint32_t prev, uint32_t curFrame, const uint32_t* rows, uint32_t nRows,
                           const uint32_t* cols, uint32_t nCols, int32_t* dots, int32_t* rowStats);
+/* FilterMatchesBySurfaceAreaCU (Bundler.cpp:175-180, SIFTImageManager.cu:318-412, cuda_surfaceArea.h, cuda_SVD.h:17-213,
+ * cuda_EigenValue.h:56-85) on the result of the last bf_matcher_filter: per side of a pair, the area of the oriented
+ * bounding box of its <= 25 filtered key points projected to their PCA plane; a pair whose two areas are both below
+ * surfAreaPcaThresh gets a filtered count of 0 (its list and transforms stay). Pairs with prev == curFrame, a filtered
+ * count of 0 or an invalid prev are skipped. opts NULL: every default. */
+int bf_match_filter_surface_area(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFMatchVerifyOptions* opts);
+/* FilterMatchesByDenseVerifyCU (Bundler.cpp:192-199, SIFTImageManager.cu:415-607, CUDACACHE_FLOAT_NORMALS branch): every
+ * pixel of prev's cache frame is carried by the pair's transform into curFrame's and every pixel of curFrame's back by
+ * the stored inverse; err = sum residual / sum weight, corr = 0.5 correspondences / (W H); a pair with
+ * corr < verifySiftCorrThresh, err > verifySiftErrThresh or NaN err gets a filtered count of 0. Skips as above.
+ * frames: DEVICE BFCachedFrame[nFrames] indexed by image index (depth, campos, normals are read; the form
+ * bf_solver_solve takes), W x H each with W, H >= 1 and W H <= 2^20; intrinsics: row-major 4x4 of the cache frames.
+ * nFrames below the matcher's image count: BF_ERR_ARG; a pair one of whose frames has a NULL depth, campos or normals
+ * pointer finds no correspondence and is rejected. The frames must be complete before the call: their producer is
+ * synchronised by the caller, as for the solver. */
+int bf_match_filter_dense_verify(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFCachedFrame* frames,
+                                 uint32_t nFrames, uint32_t W, uint32_t H, const float intrinsics[16],
+                                 const BFMatchVerifyOptions* opts);
+/* HOST read-back of pair (prev, the last curFrame) as the last calls of the two filters left it: area[2] {prev's side,
+ * cur's side}, sums[6] {sumResidual, sumWeight, numCorr} of prev -> cur, then of cur -> prev. NaN for a stage that
+ * skipped the pair or has not run. Either output may be NULL. */
+int bf_match_verify_stats(bf_matcher* m, uint32_t prev, float area[2], float sums[6]);
+/* Bundler::matchAndFilter up to filterFrames (Bundler.cpp:103-216) in one call: bf_matcher_match, bf_matcher_filter,
+ * bf_match_filter_surface_area, bf_match_filter_dense_verify, bf_matcher_filter_frames. frames NULL skips dense verify
+ * (nFrames, W, H, intrinsics are then ignored); opts NULL: every default. */
+int bf_match_and_filter(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, const BFCachedFrame* frames, uint32_t nFrames,
+                        uint32_t W, uint32_t H, const float intrinsics[16], const BFMatchVerifyOptions* opts,
+                        uint32_t* lastMatchedFrame);
+/* test hook: replaces the filtered list of pair (prev, .) by count <= 25 HOST index pairs idx[2 * count] into the linear
+ * key array (the transforms stay), so that the two filters can be given lists the Kabsch filter never lets through,
+ * such as collinear points. Synchronizes. */
+int bf_match_debug_set_filtered(bf_matcher* m, uint32_t prev, uint32_t count, const uint32_t* idx);
 int bf_matcher_synchronize(bf_matcher* m);
 int bf_matcher_timer_start(bf_matcher* m, bf_timer* t);
 int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms); /* synchronizes */

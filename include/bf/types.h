@@ -302,10 +302,24 @@ typedef struct BFMatcherOptions {
     uint32_t reserved[2];
 } BFMatcherOptions;
 
+/* Thresholds of the matcher's surface-area and dense-verify filters (bf_match_filter_*); the values of
+ * zParametersBundlingDefault.txt / zParametersDefault.txt in brackets, taken when a field is 0. */
+typedef struct BFMatchVerifyOptions {
+    float surfAreaPcaThresh;     /* s_surfAreaPcaThresh [0.032] m^2 */
+    float projCorrDistThres;     /* s_projCorrDistThres [0.15] m */
+    float projCorrNormalThres;   /* s_projCorrNormalThres [0.97] */
+    float verifySiftErrThresh;   /* s_verifySiftErrThresh [0.075] */
+    float verifySiftCorrThresh;  /* s_verifySiftCorrThresh [0.02] */
+    float sensorDepthMin;        /* s_sensorDepthMin [0.1] m */
+    float sensorDepthMax;        /* s_sensorDepthMax [4.0] m */
+    uint32_t reserved;
+} BFMatchVerifyOptions;
+
 #ifdef __cplusplus
 } /* extern "C" */
 
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
+static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
 static_assert(sizeof(BFMat4) == 64, "float4x4 is 64 B");
 static_assert(sizeof(BFHashEntry) == 32, "HashEntry is 32 B");
