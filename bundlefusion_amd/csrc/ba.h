@@ -104,6 +104,10 @@ struct SolveResult {
     uint32_t verifyOk = 0;     // ... and its outcome (1 valid)
 };
 
+namespace {
+struct BA;  // the kernels' argument block: local to ba.hip, named here for Solver's private members
+}
+
 class Solver {
 public:
     Solver(const SolverConfig& cfg, hipStream_t stream);
@@ -140,6 +144,11 @@ public:
     KernelClock& pcgClock() { return pcgClock_; }      // device time of the persistent PCG launches
 
 private:
+    // solve()'s parts (ba.hip): the kernels' argument block, the dense term's launches, and the PCG loop of a
+    // pair-mode GN step (returns the persistent launch's finisher form for k_gn_end, 0 without one)
+    BA makeArgs(const SolveArgs& s) const;
+    void buildDense(const BA& a, float wD, float wC);
+    int launchPairPcg(const BA& a, const SolveArgs& s, float wS, bool dense, unsigned pairRowGrid);
     KernelClock solveClock_;
     KernelClock pcgClock_;
     SolverConfig cfg_;

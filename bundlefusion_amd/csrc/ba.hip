@@ -1097,13 +1097,6 @@ __device__ void pcg_dense_offdiag(const BA& a, uint32_t wave, uint32_t nw) {
     for (uint32_t v = 1 + wave; v < a.N; v += nw) pcg_dense_offdiag_row<false>(a, v);
 }
 
-#ifdef BF_PCG_TIMING
-// measurement build: per PCG launch (iteration index mod 1024) the earliest workgroup start, the
-// latest phase-A end, the finisher's start and end (s_memrealtime, 100 MHz)
-__device__ unsigned long long g_pcgT[1024][4];
-__device__ unsigned long long g_pcgS[1024][6];  // the last-arriving workgroup's stage stamps (wave 0)
-__device__ unsigned long long g_pcgW[64][1024][2];  // k_pcg_persist: per iteration (< 64) and worker WG: flag seen, arrival
-#endif
 // PCG finisher (one workgroup): Kernel1b, Kernel2, the host early-out test, Kernel3
 template <int RB = 2>
 __device__ void pcg_finisher(const BA& a, float* sh, uint32_t nch, int useDense, int iter, int nLin, float& rDotzNew,
@@ -1262,72 +1255,60 @@ __global__ __launch_bounds__(WG) void k_pair_init(BA a, float wSparse) {
 }
 
 // Ap of row v (one wave), handed to the finisher write-through: k_pcg_pairs and pcg_recover
-__device__ void pair_row_ap(const BA& a, float wSparse, uint32_t v, unsigned long long* stg) {
+__device__ void pair_row_ap(const BA& a, float wSparse, uint32_t v) {
     const uint32_t lane = lane_id();
-    (void)stg;
-    {
-        const int e0 = a.rowPairStart[v], e1 = a.rowPairStart[v + 1];
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); stg[0] = rtc() + (unsigned long long)(e0 & 0); }
-#endif
-        // the row's own p and image statistics, loaded beside the pair loop (lane 0 uses them)
-        f3 pvR, pvT;
-        vload(a, V_P, v, pvR, pvT);
-        double dst[DSTAT];
+    const int e0 = a.rowPairStart[v], e1 = a.rowPairStart[v + 1];
+    // the row's own p and image statistics, loaded beside the pair loop (lane 0 uses them)
+    f3 pvR, pvT;
+    vload(a, V_P, v, pvR, pvT);
+    double dst[DSTAT];
 #pragma unroll
-        for (int q = 0; q < DSTAT; q++) dst[q] = a.dstat[(size_t)v * DSTAT + q];
-        double o[6] = {0, 0, 0, 0, 0, 0};
-        // two entries per lane per round (k and k + 64), every load of both issued before either is
-        // used: one round of dependent loads (entry, then partner p + pair statistics) per 128 entries;
-        // each lane still adds its entries in ascending k, so the sums equal the one-entry loop's
-        for (int kb = e0; kb < e1; kb += 128) {
-            const int k0 = kb + (int)lane, k1 = k0 + 64;
-            const int2 rp0 = a.rowPair[min(k0, e1 - 1)], rp1 = a.rowPair[min(k1, e1 - 1)];
-            const uint32_t u0 = (uint32_t)rp0.y & ~PAIR_A_FLAG, u1 = (uint32_t)rp1.y & ~PAIR_A_FLAG;
-            f3 pr0, pt0, pr1, pt1;
-            vload(a, V_P, u0, pr0, pt0);
-            vload(a, V_P, u1, pr1, pt1);
-            double st0[16], st1[16];
+    for (int q = 0; q < DSTAT; q++) dst[q] = a.dstat[(size_t)v * DSTAT + q];
+    double o[6] = {0, 0, 0, 0, 0, 0};
+    // two entries per lane per round (k and k + 64), every load of both issued before either is
+    // used: one round of dependent loads (entry, then partner p + pair statistics) per 128 entries;
+    // each lane still adds its entries in ascending k, so the sums equal the one-entry loop's
+    for (int kb = e0; kb < e1; kb += 128) {
+        const int k0 = kb + (int)lane, k1 = k0 + 64;
+        const int2 rp0 = a.rowPair[min(k0, e1 - 1)], rp1 = a.rowPair[min(k1, e1 - 1)];
+        const uint32_t u0 = (uint32_t)rp0.y & ~PAIR_A_FLAG, u1 = (uint32_t)rp1.y & ~PAIR_A_FLAG;
+        f3 pr0, pt0, pr1, pt1;
+        vload(a, V_P, u0, pr0, pt0);
+        vload(a, V_P, u1, pr1, pt1);
+        double st0[16], st1[16];
 #pragma unroll
-            for (int q = 0; q < 16; q += 2) {
-                const double2 x0 = *reinterpret_cast<const double2*>(a.pstat + (size_t)rp0.x * PSTAT + q);
-                const double2 x1 = *reinterpret_cast<const double2*>(a.pstat + (size_t)rp1.x * PSTAT + q);
-                st0[q] = x0.x; st0[q + 1] = x0.y;
-                st1[q] = x1.x; st1[q + 1] = x1.y;
-            }
-            if (k0 < e1 && u0 != 0) {  // p_0 = 0 (image 0 fixed)
-                const double w[3] = {pr0.x, pr0.y, pr0.z}, t[3] = {pt0.x, pt0.y, pt0.z};
-                double b[6];
-                pair_block_apply(st0, ((uint32_t)rp0.y & PAIR_A_FLAG) != 0, w, t, b);
-#pragma unroll
-                for (int q = 0; q < 6; q++) o[q] += b[q];
-            }
-            if (k1 < e1 && u1 != 0) {
-                const double w[3] = {pr1.x, pr1.y, pr1.z}, t[3] = {pt1.x, pt1.y, pt1.z};
-                double b[6];
-                pair_block_apply(st1, ((uint32_t)rp1.y & PAIR_A_FLAG) != 0, w, t, b);
-#pragma unroll
-                for (int q = 0; q < 6; q++) o[q] += b[q];
-            }
+        for (int q = 0; q < 16; q += 2) {
+            const double2 x0 = *reinterpret_cast<const double2*>(a.pstat + (size_t)rp0.x * PSTAT + q);
+            const double2 x1 = *reinterpret_cast<const double2*>(a.pstat + (size_t)rp1.x * PSTAT + q);
+            st0[q] = x0.x; st0[q + 1] = x0.y;
+            st1[q] = x1.x; st1[q + 1] = x1.y;
         }
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) stg[1] = rtc() + (unsigned long long)(o[0] != o[0]);
-#endif
+        if (k0 < e1 && u0 != 0) {  // p_0 = 0 (image 0 fixed)
+            const double w[3] = {pr0.x, pr0.y, pr0.z}, t[3] = {pt0.x, pt0.y, pt0.z};
+            double b[6];
+            pair_block_apply(st0, ((uint32_t)rp0.y & PAIR_A_FLAG) != 0, w, t, b);
 #pragma unroll
-        for (int q = 0; q < 6; q++) o[q] = wave_sum_d(o[q]);
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) stg[2] = rtc() + (unsigned long long)(o[5] != o[5]);
-#endif
-        if (lane == 0) {
-            const f3 pr = pvR, pt = pvT;
-            const double w[3] = {pr.x, pr.y, pr.z}, t[3] = {pt.x, pt.y, pt.z};
-            double dp[6];
-            diag_apply(dst, w, t, dp);
-            const double ws = wSparse;
-            float4* q = reinterpret_cast<float4*>(a.apPair + (size_t)v * 8);
-            st_wt(q, make_float4((float)(ws * (dp[0] - o[0])), (float)(ws * (dp[1] - o[1])), (float)(ws * (dp[2] - o[2])), 0.0f));
-            st_wt(q + 1, make_float4((float)(ws * (dp[3] - o[3])), (float)(ws * (dp[4] - o[4])), (float)(ws * (dp[5] - o[5])), 0.0f));
+            for (int q = 0; q < 6; q++) o[q] += b[q];
         }
+        if (k1 < e1 && u1 != 0) {
+            const double w[3] = {pr1.x, pr1.y, pr1.z}, t[3] = {pt1.x, pt1.y, pt1.z};
+            double b[6];
+            pair_block_apply(st1, ((uint32_t)rp1.y & PAIR_A_FLAG) != 0, w, t, b);
+#pragma unroll
+            for (int q = 0; q < 6; q++) o[q] += b[q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) o[q] = wave_sum_d(o[q]);
+    if (lane == 0) {
+        const f3 pr = pvR, pt = pvT;
+        const double w[3] = {pr.x, pr.y, pr.z}, t[3] = {pt.x, pt.y, pt.z};
+        double dp[6];
+        diag_apply(dst, w, t, dp);
+        const double ws = wSparse;
+        float4* q = reinterpret_cast<float4*>(a.apPair + (size_t)v * 8);
+        st_wt(q, make_float4((float)(ws * (dp[0] - o[0])), (float)(ws * (dp[1] - o[1])), (float)(ws * (dp[2] - o[2])), 0.0f));
+        st_wt(q + 1, make_float4((float)(ws * (dp[3] - o[3])), (float)(ws * (dp[4] - o[4])), (float)(ws * (dp[5] - o[5])), 0.0f));
     }
 }
 
@@ -1340,43 +1321,16 @@ template <int RB>
 __global__ __launch_bounds__(WG) void k_pcg_pairs(BA a, float wSparse, int iter, int nLin) {
     __shared__ float sh[WG];
     if (a.ctrl[K_GN_DONE] || a.ctrl[K_PCG_DONE]) return;
-#ifdef BF_PCG_TIMING
-    const unsigned long long tStart = rtc();
-    unsigned long long stg[3] = {0, 0, 0};
-#endif
     const uint32_t lane = lane_id();
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t v = 1 + wave; v < a.N; v += nw) {
-#ifdef BF_PCG_TIMING
-        pair_row_ap(a, wSparse, v, stg);
-#else
-        pair_row_ap(a, wSparse, v, nullptr);
-#endif
-    }
+    for (uint32_t v = 1 + wave; v < a.N; v += nw) pair_row_ap(a, wSparse, v);
     const int useDense = (int)a.ctrl[K_USE_DENSE];
     if (useDense) pcg_dense_offdiag(a, wave, nw);
-#ifdef BF_PCG_TIMING
-    if (threadIdx.x == 0) {
-        atomicMin(&g_pcgT[iter & 1023][0], tStart);
-        atomicMax(&g_pcgT[iter & 1023][1], rtc());
-    }
-#endif
     if (!last_block_sharded(a.sync, 1u)) return;
-#ifdef BF_PCG_TIMING
-    if (threadIdx.x == 0) {
-        g_pcgT[iter & 1023][2] = rtc();
-        unsigned long long* S = g_pcgS[iter & 1023];
-        S[0] = tStart; S[1] = stg[0]; S[2] = stg[1]; S[3] = stg[2]; S[4] = g_pcgT[iter & 1023][2];
-    }
-#endif
     if (threadIdx.x < 9) a.sync[threadIdx.x * SYNC_LINE] = 0;  // counters of the next launch
     float rDotzNew;
     bool last;
     pcg_finisher<RB>(a, sh, 0u, useDense, iter, nLin, rDotzNew, last);
-#ifdef BF_PCG_TIMING
-    __syncthreads();
-    if (threadIdx.x == 0) g_pcgT[iter & 1023][3] = rtc();
-#endif
     if (threadIdx.x == 0) {
         a.ctrl[K_RDOTZ] = __float_as_uint(rDotzNew);
         a.ctrl[K_PCG_ITERS]++;
@@ -1398,12 +1352,7 @@ __global__ __launch_bounds__(WG) void k_pcg_pairs(BA a, float wSparse, int iter,
 // last-workgroup election and two reloads of every vector. Every wait is bounded (2 s of s_memrealtime):
 // a timeout sets result error bit 3 and releases every workgroup. The grid must be co-resident: the
 // host launches it only when the occupancy query admits it with room to spare.
-#ifndef BF_PCG_PRIO
-#define BF_PCG_PRIO 2  // k_pcg_persist's wave priority (0: off)
-#endif
-#ifndef BF_PCG_PERSISTENT
-#define BF_PCG_PERSISTENT 1  // 0: one k_pcg_pairs launch per PCG iteration (A/B builds)
-#endif
+constexpr int kPcgPrio = 2;               // k_pcg_persist's wave priority
 constexpr int PP_CPL = 3;                 // cached entries per lane: rows up to 192 partner pairs stay in registers
 constexpr uint32_t PP_SHADOW = 256;       // the workgroup without rows (see the workers)
 constexpr int PP_OV = 4;                  // further entries per lane whose pair refs stay in registers (rows up to 448)
@@ -1419,34 +1368,18 @@ constexpr uint32_t PP_RECOVERED = 16u;    // K_ERROR bit 4 (BF_SOLVE_PCG_RECOVER
 // dense term is taken by R = 2 only (the host routes larger dense steps to one launch per iteration).
 // The workers' gathers of p: two 16-B buffer loads per row with the sc1 (agent-coherent) cache policy
 // — the policy of the agent-scope atomic loads in vload_t<true>, at half the L2 requests (four 8-B
-// atomics per row). Tearing cannot matter: p is complete (drained, then flagged) before any gather.
+// atomics per row). The finisher publishes p with 16-B write-through (sc1) stores, [r | tag][t | tag] (the
+// MI355X_MICROARCH.md hand-off table: 16-B sc1 stores ~ plain, 8-B ones 2.7x the time per byte).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t p_rsrc(const BA& a) {
     return __builtin_amdgcn_make_buffer_rsrc(a.vec + (size_t)V_P * a.maxN * 8, (short)0, (int)(a.maxN * 32u), 0x00020000);
-}
-__device__ __forceinline__ void pload_coh(__amdgpu_buffer_rsrc_t rs, uint32_t u, f3& r, f3& t) {
-    const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32u, 0, 16);  // 16: sc1
-    const auto y = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32u + 16u, 0, 16);
-    r = mk3(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]));
-    t = mk3(__uint_as_float(y[0]), __uint_as_float(y[1]), __uint_as_float(y[2]));
-}
-// the finisher's publication of p: 16-B write-through (sc1) stores, [r | 0][t | 0] (the
-// MI355X_MICROARCH.md hand-off table: 16-B sc1 stores ~ plain, 8-B ones 2.7x the time per byte)
-__device__ __forceinline__ void pstore_coh(__amdgpu_buffer_rsrc_t rs, uint32_t u, f3 r, f3 t) {
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    const u4 x = {__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), 0u};
-    const u4 y = {__float_as_uint(t.x), __float_as_uint(t.y), __float_as_uint(t.z), 0u};
-    __builtin_amdgcn_raw_buffer_store_b128(x, rs, u * 32u, 0, 16);  // 16: sc1
-    __builtin_amdgcn_raw_buffer_store_b128(y, rs, u * 32u + 16u, 0, 16);
 }
 
 // The p hand-off of sparse solves, without the finisher's drain and barrier: each 16-B half carries its
 // iteration's tag in the pad word (16-B sc1 halves are observed untorn, MI355X_MICROARCH.md R2), the
 // flag only says when to start gathering, and a worker re-gathers a half whose tag is stale (standalone
-// K = 500 GN iteration 1.016 / 1.050 -> 1.008 / 1.003 ms, A/B pairs; BF_PCG_PTAG=0 builds the drained
-// form, which the dense solves keep: their off-diagonal products gather p untagged).
-#ifndef BF_PCG_PTAG
-#define BF_PCG_PTAG 1
-#endif
+// K = 500 GN iteration 1.016 / 1.050 -> 1.008 / 1.003 ms, A/B pairs). The dense solves keep the drained
+// form (p complete, drained, then flagged, before any gather; tags not checked): their off-diagonal
+// products gather p untagged.
 __device__ __forceinline__ void pstore_tag(__amdgpu_buffer_rsrc_t rs, uint32_t u, f3 r, f3 t, uint32_t tag) {
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     const u4 x = {__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), tag};
@@ -1536,9 +1469,6 @@ __device__ void pcg_persist_finisher(const BA& a, float* sh, float* sM, int useD
             ok = gran_rows<H>(g, tagBase + (uint32_t)it + 1u, x, t0, a.spinTicks);
             if (ok > 0) ok = gran_rows<H>(g + H, tagBase + (uint32_t)it + 1u, x + H, t0, a.spinTicks);
         }
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) g_pcgT[it & 1023][2] = rtc();
-#endif
         float d = 0.0f;
 #pragma unroll
         for (int q = 0; q < R; q++) {
@@ -1578,9 +1508,6 @@ __device__ void pcg_persist_finisher(const BA& a, float* sh, float* sM, int useD
             if (!all) break;  // timeout: released below
             pAp = r;
         }
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) g_pcgS[it & 1023][0] = rtc();
-#endif
         const float alpha = (pAp > FLOAT_EPSILON) ? rz / pAp : 0.0f;
         // delta += alpha p is the workers' (each on its own row, from the p it gathered): alpha goes out
         // in the flag word
@@ -1608,9 +1535,6 @@ __device__ void pcg_persist_finisher(const BA& a, float* sh, float* sM, int useD
             for (uint32_t w = 0; w < WG / 64; w++) r += sh[2 * (WG / 64) + w];
             rzNew = r;
         }
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) g_pcgS[it & 1023][1] = rtc();
-#endif
         last = (it == nLin - 1) || (a.earlyOut && fabsf(pAp) < 5e-7f);
         const float beta = (rz > FLOAT_EPSILON) ? rzNew / rz : 0.0f;
 #pragma unroll
@@ -1622,28 +1546,18 @@ __device__ void pcg_persist_finisher(const BA& a, float* sh, float* sM, int useD
                 const f3 zR = mul3(mr, rR[q]), zT = mul3(mt, rT[q]);
                 pR[q] = zR + beta * pR[q];
                 pT[q] = zT + beta * pT[q];
-#if BF_PCG_PTAG
                 if (!last) pstore_tag(prs, v, pR[q], pT[q], tagBase + (uint32_t)it + 2u);  // iteration it + 1's p
-#else
-                if (!last) pstore_coh(prs, v, pR[q], pT[q]);  // the workers' next gathers
-#endif
             }
         }
         rz = rzNew;
         if (last) break;
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) g_pcgS[it & 1023][2] = rtc();
-#endif
         // p is read by ~N x 92 gathers: published write-through, drained, then one flag word
         // (p as polled granules ran 20 % slower: the workers' polls swamp the hand-off)
-        if (!BF_PCG_PTAG || useDense) {  // (the dense products gather p untagged: drained hand-off)
+        if (useDense) {  // (the dense products gather p untagged: drained hand-off)
             drain_stores();
             __syncthreads();
         }
         if (threadIdx.x < PP_NFLAG) st_wt64(flag + threadIdx.x * PP_FLAG_STRIDE, (uint32_t)(it + 1), __float_as_uint(lastAlpha));  // one instruction
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0) g_pcgT[it & 1023][3] = rtc();
-#endif
     }
     // final state (later launches read it plainly across the kernel boundary); delta and the Lie
     // update are the workers'
@@ -1741,9 +1655,6 @@ __device__ void pcg_persist_finisher_x4(const BA& a, float* sh, int nLin, uint32
         }
         float x[R][6];
         const int got = gran_rows<R>(gp, tag, x, t0, a.spinTicks);
-#ifdef BF_PCG_TIMING
-        if (g == 0 && threadIdx.x == 0) g_pcgT[it & 1023][2] = rtc();
-#endif
         float d = 0.0f;
 #pragma unroll
         for (int q = 0; q < R; q++)
@@ -1762,9 +1673,6 @@ __device__ void pcg_persist_finisher_x4(const BA& a, float* sh, int nLin, uint32
         bool ok;
         const float pAp = fx_exchange(a, sh, 0, g, S, tag, t0, ok);
         if (!ok) break;
-#ifdef BF_PCG_TIMING
-        if (g == 0 && threadIdx.x == 0) g_pcgS[it & 1023][0] = rtc();
-#endif
         const float alpha = (pAp > FLOAT_EPSILON) ? rz / pAp : 0.0f;
         lastAlpha = alpha;
         float b = 0.0f;
@@ -1787,9 +1695,6 @@ __device__ void pcg_persist_finisher_x4(const BA& a, float* sh, int nLin, uint32
         }
         const float rzNew = fx_exchange(a, sh, 1, g, S2, tag, t0, ok);
         if (!ok) break;
-#ifdef BF_PCG_TIMING
-        if (g == 0 && threadIdx.x == 0) g_pcgS[it & 1023][1] = rtc();
-#endif
         last = (it == nLin - 1) || (a.earlyOut && fabsf(pAp) < 5e-7f);
         const float beta = (rz > FLOAT_EPSILON) ? rzNew / rz : 0.0f;
 #pragma unroll
@@ -1804,15 +1709,9 @@ __device__ void pcg_persist_finisher_x4(const BA& a, float* sh, int nLin, uint32
         }
         rz = rzNew;
         if (last) break;
-#ifdef BF_PCG_TIMING
-        if (g == 0 && threadIdx.x == 0) g_pcgS[it & 1023][2] = rtc();
-#endif
         // the flag only says when to start gathering: the p halves of the other finishers' rows carry
         // their tag, and a worker re-gathers a stale one
         if (g == 0 && threadIdx.x < PP_NFLAG) st_wt64(flag + threadIdx.x * PP_FLAG_STRIDE, (uint32_t)(it + 1), __float_as_uint(lastAlpha));
-#ifdef BF_PCG_TIMING
-        if (g == 0 && threadIdx.x == 0) g_pcgT[it & 1023][3] = rtc();
-#endif
     }
 #pragma unroll
     for (int q = 0; q < R; q++) {
@@ -1845,13 +1744,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
     __shared__ double sD[WG / 64][DSTAT];          // each worker wave's image statistics
     if (a.ctrl[K_GN_DONE] || a.ctrl[K_PCG_DONE]) return;  // uniform over the grid (set by earlier launches)
     const uint32_t lane = lane_id();
-#if BF_PCG_PRIO
     // above the voxel pass's waves on the same CU (its op steps run at 1): an iteration's critical path is
     // this kernel's compute between hand-offs, and its waits sleep (s_sleep), so the raise costs the voxel
     // pass little: in-loop time per PCG iteration 7.67 -> 6.43 us (1.46x -> 1.23x standalone), frame rate
     // 1 576 -> 1 587 at the driver workload (profiles/r11_prio_ab.txt)
-    __builtin_amdgcn_s_setprio(BF_PCG_PRIO);
-#endif
+    __builtin_amdgcn_s_setprio(kPcgPrio);
     const int useDense = (int)a.ctrl[K_USE_DENSE];
     const unsigned long long t0 = rtc();
     uint32_t* flag = &a.sync[SYNC_FLAGR];
@@ -1909,7 +1806,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
             // p of iteration it (the previous launch's, or the finisher's write-through stores)
             f3 pr[PP_CPL], pt[PP_CPL];
             const uint32_t tag = tagBase + it + 1u;
-#if BF_PCG_PTAG
             {   // every gather in flight at once, then all of them again while any is stale (rows u = 0,
                 // whose p is never written, and p of an earlier launch, it = 0, carry no tag)
                 const bool chk = it > 0 && !useDense;
@@ -1925,11 +1821,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
                     __builtin_amdgcn_s_sleep(1);
                 }
             }
-#else
-#pragma unroll
-            for (int c = 0; c < PP_CPL; c++) pload_coh(prs, (uint32_t)rp[c].y & ~PAIR_A_FLAG, pr[c], pt[c]);
-            pload_coh(prs, v, pvR, pvT);
-#endif
             double o[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int c = 0; c < PP_CPL; c++) {
@@ -1950,11 +1841,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
                 const uint32_t u = (uint32_t)rq[c].y & ~PAIR_A_FLAG;
                 if (u == 0) continue;
                 f3 qr, qt;
-#if BF_PCG_PTAG
                 pload_wait(a, prs, u, qr, qt, tag, it > 0 && !useDense, t0);
-#else
-                pload_coh(prs, u, qr, qt);
-#endif
                 const double w[3] = {qr.x, qr.y, qr.z}, t[3] = {qt.x, qt.y, qt.z};
                 double bb[6];
                 // the pair's statistics address formed here, each iteration: hoisted out of the loop it was spilled
@@ -1970,11 +1857,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
                 const uint32_t u = (uint32_t)r2.y & ~PAIR_A_FLAG;
                 if (u == 0) continue;
                 f3 qr, qt;
-#if BF_PCG_PTAG
                 pload_wait(a, prs, u, qr, qt, tag, it > 0 && !useDense, t0);
-#else
-                pload_coh(prs, u, qr, qt);
-#endif
                 const double w[3] = {qr.x, qr.y, qr.z}, t[3] = {qt.x, qt.y, qt.z};
                 double bb[6];
                 pair_block_apply(a.pstat + (size_t)r2.x * PSTAT, ((uint32_t)r2.y & PAIR_A_FLAG) != 0, w, t, bb);
@@ -1997,9 +1880,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
             if (useDense) pcg_dense_offdiag_row<true>(a, v, tag);
         }
         // every wave polls its own flag replica (no workgroup barrier per iteration): one load per poll
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0 && it < 64 && blockIdx.x < 1024) g_pcgW[it][blockIdx.x][1] = rtc();  // plain per-WG stamps
-#endif
         uint32_t f, fa = 0;
         for (;;) {
             const uint64_t fw = ld_wt64(myFlag);
@@ -2009,9 +1889,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
             if (pp_timed_out(t0, a.spinTicks)) { f = PP_DONE; break; }
             __builtin_amdgcn_s_sleep(1);
         }
-#ifdef BF_PCG_TIMING
-        if (threadIdx.x == 0 && !(f & PP_DONE) && it + 1 < 64 && blockIdx.x < 1024) g_pcgW[it + 1][blockIdx.x][0] = rtc();
-#endif
         // alpha of this iteration, in the flag word (PP_DONE carries how many iterations ran: the
         // flag seen here is exactly iteration it's, as the finisher's next one needs this row's Ap)
         const bool haveAlpha = !(f & PP_DONE) || (f & ~PP_DONE) > it;
@@ -2063,7 +1940,7 @@ __device__ __forceinline__ void pcg_recover(const BA& a, float* sh, float wSpars
     __syncthreads();
     const int useDense = (int)a.ctrl[K_USE_DENSE];
     for (int iter = 0; iter < nLin; iter++) {
-        for (uint32_t v = 1 + wave; v < a.N; v += nw) pair_row_ap(a, wSparse, v, nullptr);
+        for (uint32_t v = 1 + wave; v < a.N; v += nw) pair_row_ap(a, wSparse, v);
         if (useDense) pcg_dense_offdiag(a, wave, nw);
         __syncthreads();
         float rDotzNew;
@@ -2961,9 +2838,6 @@ Solver::Solver(const SolverConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_
     BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occP, k_pcg_persist<2>, WG, 0));
     BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occP8, k_pcg_persist<2, PP_NF>, WG, 0));
     persistCapacity_ = (unsigned)std::max(std::min(occP, occP8), 0) * (unsigned)numCUs_;
-#ifdef BF_PCG_TIMING
-    fprintf(stderr, "k_pcg_persist occupancy: <2> %d, <8> %d workgroups per CU, %d CUs\n", occP, occP8, numCUs_);
-#endif
     BF_HIP(hipMemsetAsync(vec_.p, 0, vec_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(ctrl_.p, 0, ctrl_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(sync_.p, 0, sync_.bytes(), stream_));
@@ -3005,11 +2879,8 @@ uint32_t Solver::exportPairs(double* stats, int* pairAB, uint32_t cap) {
     return np;
 }
 
-// CUDASolverBundling::solve (CUDASolverBundling.cpp:187-284) -> solveBundlingStub (SolverBundling.cu:1137-1220)
-void Solver::solve(const SolveArgs& s) {
-    BF_REQUIRE(s.numImages > 1 && s.numImages <= cfg_.maxImages, BF_ERR_ARG, "numImages out of range");
-    BF_REQUIRE(s.numCorr <= cfg_.maxCorr, BF_ERR_CAPACITY, "numCorr exceeds solver capacity");
-    BF_REQUIRE(s.nNonLin > 0 && s.wSparse, BF_ERR_ARG, "nNonLin / weights");
+// the kernels' argument block of one solve (pairMode and pairBound are solve()'s)
+BA Solver::makeArgs(const SolveArgs& s) const {
     BA a{};
     a.corr = s.corr; a.nCorr = s.numCorr; a.valid = s.valid; a.N = s.numImages; a.maxN = cfg_.maxImages; a.cap = maxCorrPerImage_;
     a.rowCount = rowCount_.p; a.rowStart = rowStart_.p; a.rowLen = rowLen_.p; a.rowTmp = rowTmp_.p; a.rowIdx = rowIdx_.p;
@@ -3036,11 +2907,86 @@ void Solver::solve(const SolveArgs& s) {
     a.earlyOut = cfg_.earlyOut ? 1u : 0u;
     a.poseBak = poseBak_.p;
     a.spinTicks = cfg_.pcgSpinLimitUs ? 100ull * cfg_.pcgSpinLimitUs : PP_SPIN_TICKS;
-    // assembled normal equations for sparse-only solves (auto) unless the matrix-free path is forced
-    bool denseAny = false;
-    for (uint32_t it = 0; it < s.nNonLin && s.cache; it++)
-        denseAny = denseAny || (s.wDenseDepth && s.wDenseDepth[it] > 0.0f) || (s.wDenseColor && s.wDenseColor[it] > 0.0f);
-    (void)denseAny;
+    return a;
+}
+
+// the dense term of a GN step: overlapping image pairs, then their normal-equation blocks and per-image lists
+void Solver::buildDense(const BA& a, float wD, float wC) {
+    k_dense_reset<<<64, WG, 0, stream_>>>(a);
+    k_dense_overlap<<<dim3(a.N, a.N), 64, 0, stream_>>>(a);
+    k_dense_compact<<<1, 256, 0, stream_>>>(a);
+    k_dense_count<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 8), WG, 0, stream_>>>(a);
+    k_dense_build<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 4), WG, 0, stream_>>>(a, wD, wC);
+    k_dense_lists<<<a.N, 64, 0, stream_>>>(a);
+    BF_LAUNCH_CHECK();
+}
+
+// The PCG loop of a pair-mode GN step. Returns the finisher form (image rows per thread, 2 or 8) of a
+// persistent launch, with which k_gn_end redoes a timed-out step; 0 when there was no persistent launch.
+int Solver::launchPairPcg(const BA& a, const SolveArgs& s, float wS, bool dense, unsigned pairRowGrid) {
+    if (s.numImages <= (uint32_t)SMALL_N) {
+        if (s.nLin) k_pcg_small<<<1, SMALL_WG, 0, stream_>>>(a, wS, (int)s.nLin);
+        return 0;
+    }
+    // one launch for the GN step's PCG loop when its grid is co-resident: up to 513 images
+    // (one finisher workgroup, rows in registers, dense term included) with room to spare; up
+    // to 2 017 sparse-only (config 4's 2 001 keyframes) with PP_NF finisher workgroups within
+    // the occupancy query's capacity (persistent launches are serialized per device, below)
+    const bool smallN = s.numImages <= 2u * WG + 1u;
+    const unsigned nF = smallN ? 1u : (unsigned)PP_NF;
+    const unsigned nW = div_up(s.numImages - 1u, (unsigned)(WG / 64));
+    unsigned persistGrid = nF + nW;
+    if (persistGrid > PP_SHADOW) persistGrid += nF;  // the row-less workgroups on the finishers' CUs
+    const bool small = smallN && persistGrid * 2u <= persistCapacity_;
+    // the PP_NF finishers own rows 1 .. 2 * PP_NF * WG: beyond that no finisher would tag a row's p
+    const bool wide = !smallN && !dense && s.numImages <= 2u * (unsigned)PP_NF * WG + 1u && persistGrid <= persistCapacity_;
+    if (cfg_.pcgLaunch != 0 || s.nLin >= 255u || !(small || wide)) {  // one launch per PCG iteration
+        if (smallN)
+            for (uint32_t li = 0; li < s.nLin; li++) k_pcg_pairs<2><<<pairRowGrid, WG, 0, stream_>>>(a, wS, (int)li, (int)s.nLin);
+        else
+            for (uint32_t li = 0; li < s.nLin; li++) k_pcg_pairs<8><<<pairRowGrid, WG, 0, stream_>>>(a, wS, (int)li, (int)s.nLin);
+        return 0;
+    }
+    if (!s.nLin) return 0;
+    // ranks of a loopback group (one GPU) issue their persistent launches in rank order
+    struct Turn {
+        Comm* c;
+        explicit Turn(Comm* x) : c(x) { if (c) c->orderedLaunchBegin(); }
+        ~Turn() { if (c) c->orderedLaunchEnd(); }
+    } turn(comm_ && comm_->size() > 1 ? comm_ : nullptr);
+    // persistent launches of every solver on this device run one at a time: two
+    // partly resident persistent grids could each wait on the other's workgroups
+    PersistGate& pg = persist_gate();
+    std::lock_guard<std::mutex> lk(pg.mu);
+    // always wait, on the same stream too: a destroyed solver's stream handle may be
+    // reused by a new solver whose launch must still follow the old one (cheap in order)
+    if (pg.ev) BF_HIP(hipStreamWaitEvent(stream_, pg.ev, 0));
+    // dispatch-stamped events (pcgClock): the launch's own device time, for the in-loop
+    // time per PCG iteration beside the standalone one
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timed = pcgClock_.enabled();
+    if (timed) pcgClock_.slot(e0, e1);
+    if (small)
+        hipExtLaunchKernelGGL(k_pcg_persist<2>, dim3(persistGrid), dim3(WG), 0, stream_, e0, e1, 0, a, wS, (int)s.nLin, pcgEpoch_);
+    else
+        hipExtLaunchKernelGGL((k_pcg_persist<2, PP_NF>), dim3(persistGrid), dim3(WG), 0, stream_, e0, e1, 0, a, wS, (int)s.nLin,
+                              pcgEpoch_);
+    BF_LAUNCH_CHECK();
+    if (timed) pcgClock_.commit();
+    if (!pg.ev) BF_HIP(hipEventCreateWithFlags(&pg.ev, hipEventDisableTiming));
+    BF_HIP(hipEventRecord(pg.ev, stream_));
+    pg.stream = stream_;
+    pcgEpoch_ = (pcgEpoch_ + 1) & 0xFFFFFFu;
+    return smallN ? 2 : 8;
+}
+
+// CUDASolverBundling::solve (CUDASolverBundling.cpp:187-284) -> solveBundlingStub (SolverBundling.cu:1137-1220)
+void Solver::solve(const SolveArgs& s) {
+    BF_REQUIRE(s.numImages > 1 && s.numImages <= cfg_.maxImages, BF_ERR_ARG, "numImages out of range");
+    BF_REQUIRE(s.numCorr <= cfg_.maxCorr, BF_ERR_CAPACITY, "numCorr exceeds solver capacity");
+    BF_REQUIRE(s.nNonLin > 0 && s.wSparse, BF_ERR_ARG, "nNonLin / weights");
+    BA a = makeArgs(s);
+    // assembled normal equations unless the matrix-free path is forced
     const bool pairMode = cfg_.normalEquations != 1;
     BF_REQUIRE(pairMode || shardCount_ == 1, BF_ERR_ARG, "sharded solves use the assembled normal equations");
     a.pairMode = pairMode ? 1u : 0u;
@@ -3107,204 +3053,12 @@ void Solver::solve(const SolveArgs& s) {
         if (!transformsDone) k_transforms<<<div_up(s.numImages, 64), 64, 0, stream_>>>(a, wS, dense ? 1 : 0, 1, 1);
         transformsDone = nextW > 0.0f;
         if (pairMode) {
-            if (dense) {
-                k_dense_reset<<<64, WG, 0, stream_>>>(a);
-                k_dense_overlap<<<dim3(s.numImages, s.numImages), 64, 0, stream_>>>(a);
-                k_dense_compact<<<1, 256, 0, stream_>>>(a);
-                k_dense_count<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 8), WG, 0, stream_>>>(a);
-                k_dense_build<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 4), WG, 0, stream_>>>(a, wD, wC);
-                k_dense_lists<<<s.numImages, 64, 0, stream_>>>(a);
-                BF_LAUNCH_CHECK();
-            }
+            if (dense) buildDense(a, wD, wC);
             k_pair_stats<<<(unsigned)numCUs_ * 4, WG, 0, stream_>>>(a);
             BF_LAUNCH_CHECK();
             if (comm_ && comm_->size() > 1) comm_->allreduceSum(pstat_.p, (size_t)bound * PSTAT, stream_);
             k_pair_init<<<pairRowGrid, WG, 0, stream_>>>(a, wS);
-            int recoverRB = 0;  // the finisher form of a persistent launch this GN step
-            if (s.numImages <= (uint32_t)SMALL_N) {
-                if (s.nLin) k_pcg_small<<<1, SMALL_WG, 0, stream_>>>(a, wS, (int)s.nLin);
-            } else {
-                // one launch for the GN step's PCG loop when its grid is co-resident: up to 513 images
-                // (one finisher workgroup, rows in registers, dense term included) with room to spare; up
-                // to 2 017 sparse-only (config 4's 2 001 keyframes) with PP_NF finisher workgroups within
-                // the occupancy query's capacity (persistent launches are serialized per device, below)
-                const bool smallN = s.numImages <= 2u * WG + 1u;
-                const unsigned nF = smallN ? 1u : (unsigned)PP_NF;
-                const unsigned nW = div_up(s.numImages - 1u, (unsigned)(WG / 64));
-                unsigned persistGrid = nF + nW;
-                if (persistGrid > PP_SHADOW) persistGrid += nF;  // the row-less workgroups on the finishers' CUs
-                const bool small = smallN && persistGrid * 2u <= persistCapacity_;
-                // the PP_NF finishers own rows 1 .. 2 * PP_NF * WG: beyond that no finisher would tag a row's p
-                const bool wide = !smallN && !dense && s.numImages <= 2u * (unsigned)PP_NF * WG + 1u &&
-                                  persistGrid <= persistCapacity_;
-                if (BF_PCG_PERSISTENT && cfg_.pcgLaunch == 0 && s.nLin < 255u && s.numImages >= 2u && (small || wide)) {
-#ifdef BF_PCG_TIMING
-                    {
-                        std::vector<unsigned long long> z(1024 * 4, 0ull);
-                        BF_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_pcgT), z.data(), z.size() * 8, 0, hipMemcpyHostToDevice, stream_));
-                    }
-#endif
-                    if (s.nLin) {
-                        // ranks of a loopback group (one GPU) issue their persistent launches in rank order
-                        struct Turn {
-                            Comm* c;
-                            explicit Turn(Comm* x) : c(x) { if (c) c->orderedLaunchBegin(); }
-                            ~Turn() { if (c) c->orderedLaunchEnd(); }
-                        } turn(comm_ && comm_->size() > 1 ? comm_ : nullptr);
-                        // persistent launches of every solver on this device run one at a time: two
-                        // partly resident persistent grids could each wait on the other's workgroups
-                        PersistGate& pg = persist_gate();
-                        std::lock_guard<std::mutex> lk(pg.mu);
-                        // always wait, on the same stream too: a destroyed solver's stream handle may be
-                        // reused by a new solver whose launch must still follow the old one (cheap in order)
-                        if (pg.ev) BF_HIP(hipStreamWaitEvent(stream_, pg.ev, 0));
-                        // dispatch-stamped events (pcgClock): the launch's own device time, for the in-loop
-                        // time per PCG iteration beside the standalone one
-                        hipEvent_t e0 = nullptr, e1 = nullptr;
-                        const bool timed = pcgClock_.enabled();
-                        if (timed) pcgClock_.slot(e0, e1);
-                        if (small)
-                            hipExtLaunchKernelGGL(k_pcg_persist<2>, dim3(persistGrid), dim3(WG), 0, stream_, e0, e1, 0, a, wS,
-                                                  (int)s.nLin, pcgEpoch_);
-                        else
-                            hipExtLaunchKernelGGL((k_pcg_persist<2, PP_NF>), dim3(persistGrid), dim3(WG), 0, stream_, e0, e1, 0, a,
-                                                  wS, (int)s.nLin, pcgEpoch_);
-                        BF_LAUNCH_CHECK();
-                        if (timed) pcgClock_.commit();
-                        if (!pg.ev) BF_HIP(hipEventCreateWithFlags(&pg.ev, hipEventDisableTiming));
-                        BF_HIP(hipEventRecord(pg.ev, stream_));
-                        pg.stream = stream_;
-                        pcgEpoch_ = (pcgEpoch_ + 1) & 0xFFFFFFu;
-                        recoverRB = s.numImages <= 2u * WG + 1u ? 2 : 8;  // k_gn_end redoes a timed-out step
-                    }
-#ifdef BF_PCG_TIMING
-                    {
-                        std::vector<unsigned long long> t(1024 * 4);
-                        BF_HIP(hipMemcpyFromSymbolAsync(t.data(), HIP_SYMBOL(g_pcgT), t.size() * 8, 0, hipMemcpyDeviceToHost, stream_));
-                        BF_HIP(hipStreamSynchronize(stream_));
-                        {   // per-WG stamps (iterations < 64): maxima into t[.][0..1]; spread and per-WG work time
-                            std::vector<unsigned long long> W(64 * 1024 * 2);
-                            BF_HIP(hipMemcpyFromSymbol(W.data(), HIP_SYMBOL(g_pcgW), W.size() * 8));
-                            double spreadSeen = 0, spreadArr = 0, meanWork = 0, maxWork = 0; int nq = 0;
-                            for (uint32_t q = 1; q < 63 && q + 2 < s.nLin; q++) {
-                                unsigned long long s0 = ~0ull, s1 = 0, a0 = ~0ull, a1 = 0; double wsum = 0, wmax = 0; int nw = 0, bmax = 0;
-                                for (uint32_t b = 1; b < persistGrid && b < 1024; b++) {
-                                    if (b == PP_SHADOW) continue;  // no rows
-                                    const unsigned long long fs = W[(q * 1024 + b) * 2], ar = W[(q * 1024 + b) * 2 + 1];
-                                    if (!fs || !ar) continue;
-                                    s0 = std::min(s0, fs); s1 = std::max(s1, fs); a0 = std::min(a0, ar); a1 = std::max(a1, ar);
-                                    if ((double)ar - (double)fs > wmax) bmax = (int)b;
-                                    wsum += (double)ar - (double)fs; wmax = std::max(wmax, (double)ar - (double)fs); nw++;
-                                }
-                                if (!nw) continue;
-                                if (q < 6) {  // the slowest workgroups of a few iterations
-                                    std::vector<std::pair<double, int>> v;
-                                    for (uint32_t b = 1; b < persistGrid && b < 1024; b++) {
-                                    if (b == PP_SHADOW) continue;  // no rows
-                                        const unsigned long long fs = W[(q * 1024 + b) * 2], ar = W[(q * 1024 + b) * 2 + 1];
-                                        if (fs && ar) v.push_back({((double)ar - (double)fs) / 100, (int)b});
-                                    }
-                                    std::sort(v.rbegin(), v.rend());
-                                    fprintf(stderr, "  iteration %u slowest WGs (us:block):", q);
-                                    for (size_t k = 0; k < v.size() && k < 8; k++) fprintf(stderr, " %.2f:%d", v[k].first, v[k].second);
-                                    fprintf(stderr, "\n");
-                                    std::vector<std::pair<double, int>> fsv;
-                                    for (uint32_t b = 1; b < persistGrid && b < 1024; b++) {
-                                    if (b == PP_SHADOW) continue;  // no rows
-                                        const unsigned long long fs = W[(q * 1024 + b) * 2];
-                                        if (fs) fsv.push_back({((double)fs - (double)s0) / 100, (int)b});
-                                    }
-                                    std::sort(fsv.rbegin(), fsv.rend());
-                                    fprintf(stderr, "  iteration %u latest flag-seen WGs (us after first:block):", q);
-                                    for (size_t k = 0; k < fsv.size() && k < 12; k++) fprintf(stderr, " %.2f:%d", fsv[k].first, fsv[k].second);
-                                    int late = 0;
-                                    for (auto& e : fsv) late += e.first > 2.0;
-                                    fprintf(stderr, "  (%d WGs > 2 us)\n", late);
-                                }
-                                (void)bmax;
-                                t[q * 4] = s1; t[q * 4 + 1] = a1;
-                                spreadSeen += (double)(s1 - s0); spreadArr += (double)(a1 - a0); meanWork += wsum / nw; maxWork += wmax; nq++;
-                            }
-                            for (uint32_t q = 64; q < 1024; q++) t[q * 4] = t[q * 4 + 1] = 0;
-                            if (nq) fprintf(stderr, "  workers (us, iterations 1-62): flag-seen spread %.2f  arrival spread %.2f  per-WG work mean %.2f  max %.2f\n",
-                                            spreadSeen / nq / 100, spreadArr / nq / 100, meanWork / nq / 100, maxWork / nq / 100);
-                        }
-                        // per iteration q: [0] latest worker saw the flag of q, [1] latest worker arrival of q,
-                        // [2] finisher saw all arrivals of q, [3] finisher published q + 1
-                        double w = 0, ar = 0, fi = 0, bc = 0; int n = 0;
-                        for (uint32_t q = 1; q + 2 < s.nLin && q < 1023; q++) {
-                            const unsigned long long* r = &t[q * 4];
-                            const unsigned long long* nx = &t[(q + 1) * 4];
-                            if (!r[0] || !r[1] || !r[2] || !r[3] || !nx[0]) continue;
-                            w += (double)r[1] - (double)r[0]; ar += (double)r[2] - (double)r[1];
-                            fi += (double)r[3] - (double)r[2]; bc += (double)nx[0] - (double)r[3]; n++;
-                        }
-                        if (n) fprintf(stderr, "persistent pcg (us, mean over %d iterations): workers flag->arrive %.2f  arrival->finisher %.2f  finisher %.2f  flag->last worker %.2f  total %.2f\n",
-                                       n, w / n / 100, ar / n / 100, fi / n / 100, bc / n / 100, (w + ar + fi + bc) / n / 100);
-                        std::vector<unsigned long long> g(1024 * 6);
-                        BF_HIP(hipMemcpyFromSymbol(g.data(), HIP_SYMBOL(g_pcgS), g.size() * 8));
-                        double f0 = 0, f1 = 0, f2 = 0, f3v = 0; int m = 0;
-                        for (uint32_t q = 1; q + 2 < s.nLin && q < 1023; q++) {
-                            const unsigned long long* r = &t[q * 4];
-                            const unsigned long long* G = &g[q * 6];
-                            if (!r[2] || !r[3] || !G[0] || !G[1] || !G[2]) continue;
-                            f0 += (double)G[0] - (double)r[2]; f1 += (double)G[1] - (double)G[0];
-                            f2 += (double)G[2] - (double)G[1]; f3v += (double)r[3] - (double)G[2]; m++;
-                        }
-                        if (m) fprintf(stderr, "  finisher (us): Ap + pAp sum %.2f  delta/r/z + rz sum %.2f  p + stores %.2f  drain + flag %.2f\n",
-                                       f0 / m / 100, f1 / m / 100, f2 / m / 100, f3v / m / 100);
-                        std::vector<int> rps(s.numImages + 1);
-                        BF_HIP(hipMemcpy(rps.data(), rowPairStart_.p, rps.size() * 4, hipMemcpyDeviceToHost));
-                        int dmax = 0, over192 = 0, over448 = 0;
-                        for (uint32_t q = 1; q < s.numImages; q++) {
-                            const int dg = rps[q + 1] - rps[q];
-                            dmax = std::max(dmax, dg); over192 += dg > 192; over448 += dg > 448;
-                        }
-                        fprintf(stderr, "  row degrees: mean %.1f  max %d  rows > 192: %d  > 448: %d\n",
-                                (double)(rps[s.numImages] - rps[1]) / (s.numImages - 1), dmax, over192, over448);
-                    }
-#endif
-                } else if (s.numImages <= 2u * WG + 1u) {
-#ifdef BF_PCG_TIMING
-                    {
-                        std::vector<unsigned long long> init(1024 * 4);
-                        for (int q = 0; q < 1024; q++) { init[q * 4] = ~0ull; init[q * 4 + 1] = 0; init[q * 4 + 2] = 0; init[q * 4 + 3] = 0; }
-                        BF_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_pcgT), init.data(), init.size() * 8, 0, hipMemcpyHostToDevice, stream_));
-                    }
-#endif
-                    for (uint32_t li = 0; li < s.nLin; li++) k_pcg_pairs<2><<<pairRowGrid, WG, 0, stream_>>>(a, wS, (int)li, (int)s.nLin);
-#ifdef BF_PCG_TIMING
-                    {
-                        std::vector<unsigned long long> t(1024 * 4);
-                        BF_HIP(hipMemcpyFromSymbolAsync(t.data(), HIP_SYMBOL(g_pcgT), t.size() * 8, 0, hipMemcpyDeviceToHost, stream_));
-                        BF_HIP(hipStreamSynchronize(stream_));
-                        double sA = 0, sW = 0, sF = 0, sAll = 0; int n = 0;
-                        for (uint32_t q = 1; q + 1 < s.nLin && q < 1024; q++) {
-                            const unsigned long long* r = &t[q * 4];
-                            const unsigned long long* nx = &t[(q + 1) * 4];
-                            if (!r[3] || !nx[3] || r[0] == ~0ull) continue;
-                            sA += (double)(r[1] - r[0]); sW += (double)(r[2] - r[1]); sF += (double)(r[3] - r[2]);
-                            sAll += (double)(nx[0] - r[0]); n++;
-                        }
-                        if (n) fprintf(stderr, "pcg timing (us, mean over %d launches): phase A %.2f  arrival %.2f  finisher %.2f  start-to-next-start %.2f\n",
-                                       n, sA / n / 100.0, sW / n / 100.0, sF / n / 100.0, sAll / n / 100.0);
-                        std::vector<unsigned long long> g(1024 * 6);
-                        BF_HIP(hipMemcpyFromSymbol(g.data(), HIP_SYMBOL(g_pcgS), g.size() * 8));
-                        double d0 = 0, d1 = 0, d2 = 0, d3 = 0, sk = 0; int m = 0;
-                        for (uint32_t q = 1; q + 1 < s.nLin && q < 1024; q++) {
-                            const unsigned long long* G = &g[q * 6];
-                            if (!G[4] || !G[1] || !G[2] || !G[3]) continue;
-                            sk += (double)(G[0] - t[q * 4]); d0 += (double)(G[1] - G[0]); d1 += (double)(G[2] - G[1]);
-                            d2 += (double)(G[3] - G[2]); d3 += (double)(G[4] - G[3]); m++;
-                        }
-                        if (m) fprintf(stderr, "  last WG (us): start skew %.2f  row start loads %.2f  pair loop %.2f  wave sums %.2f  diag+store+arrival %.2f\n",
-                                       sk / m / 100.0, d0 / m / 100.0, d1 / m / 100.0, d2 / m / 100.0, d3 / m / 100.0);
-                    }
-#endif
-                } else {
-                    for (uint32_t li = 0; li < s.nLin; li++) k_pcg_pairs<8><<<pairRowGrid, WG, 0, stream_>>>(a, wS, (int)li, (int)s.nLin);
-                }
-            }
+            const int recoverRB = launchPairPcg(a, s, wS, dense, pairRowGrid);  // k_gn_end redoes a timed-out persistent step
             BF_LAUNCH_CHECK();
             if (recoverRB == 2) k_gn_end<2><<<1, WG, 0, stream_>>>(a, (int)it, (int)s.nNonLin, wS, (int)s.nLin, nextW);
             else if (recoverRB == 8) k_gn_end<8><<<1, WG, 0, stream_>>>(a, (int)it, (int)s.nNonLin, wS, (int)s.nLin, nextW);
@@ -3312,15 +3066,7 @@ void Solver::solve(const SolveArgs& s) {
             BF_LAUNCH_CHECK();
             continue;
         }
-        if (dense) {
-            k_dense_reset<<<64, WG, 0, stream_>>>(a);
-            k_dense_overlap<<<dim3(s.numImages, s.numImages), 64, 0, stream_>>>(a);
-            k_dense_compact<<<1, 256, 0, stream_>>>(a);
-            k_dense_count<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 8), WG, 0, stream_>>>(a);
-            k_dense_build<<<std::min(a.maxPairs, (uint32_t)numCUs_ * 4), WG, 0, stream_>>>(a, wD, wC);
-            k_dense_lists<<<s.numImages, 64, 0, stream_>>>(a);
-            BF_LAUNCH_CHECK();
-        }
+        if (dense) buildDense(a, wD, wC);
         k_entries<<<rowGrid, WG, 0, stream_>>>(a);
         k_init<<<rowGrid, WG, 0, stream_>>>(a, wS);
         BF_LAUNCH_CHECK();

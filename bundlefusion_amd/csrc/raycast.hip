@@ -350,33 +350,17 @@ __global__ __launch_bounds__(256) void k_splat_tiles(const int4* __restrict__ qu
     }
 }
 
-// getVoxel(worldPos) (VoxelUtilHashSDF.h:406-417)'s block lookup with a two-entry per-thread block cache: a
-// trilinear sample's corners straddle a block face about a third of the time, and a one-entry cache re-probed
-// the hash as the corners alternated between the two blocks
-#ifndef BF_RENDER_CACHE
-#define BF_RENDER_CACHE 1  // per-thread register cache entries (A/B builds: 2)
-#endif
+// getVoxel(worldPos) (VoxelUtilHashSDF.h:406-417)'s block lookup: a one-entry per-thread register cache (the
+// block of the last lookup), then the workgroup's LDS block table, then the hash. One entry, because with one
+// the kernel without gradients fits 5 waves per SIMD (k_render's comment); the misses it leaves go to the LDS
+// table, which keeps the hash probes at 1.41 M per render (2.43 M without it, profiles/r10_raycast_lds_table_ab.txt)
 struct BlockCache {
-    int ax = INT_MIN, ay = 0, az = 0, ap = BF_FREE_ENTRY;  // entry A
-#if BF_RENDER_CACHE == 2
-    int bx = INT_MIN, by = 0, bz = 0, bp = BF_FREE_ENTRY;  // entry B
-    bool replaceB = false;  // the entry a miss replaces (the one not used last)
-#endif
+    int ax = INT_MIN, ay = 0, az = 0, ap = BF_FREE_ENTRY;  // the cached block and its heap index
     uint32_t samples = 0, loads = 0, probes = 0;  // render statistics (trilinear samples, voxel loads, hash probes)
     unsigned long long* table = nullptr;  // the workgroup's LDS block table (nullptr: probe every miss)
     __device__ __forceinline__ int lookup(const RayArgs& R, i3 b) {
-        // hits and updates as register selects: written as branches on the two entries, the compiler kept the
-        // pair {ap, bp} in scratch and read it back on every hit (a memory round trip per corner lookup)
-        const bool hitA = b.x == ax && b.y == ay && b.z == az;
-#if BF_RENDER_CACHE == 2
-        const bool hitB = b.x == bx && b.y == by && b.z == bz;
-        if (hitA || hitB) {
-            replaceB = hitA;
-            return hitA ? ap : bp;
-        }
-#else
-        if (hitA) return ap;
-#endif
+        const bool hit = b.x == ax && b.y == ay && b.z == az;
+        if (hit) return ap;
         int p;
         unsigned long long key;
         const bool keyed = table && rc_key(b, key);
@@ -390,14 +374,7 @@ struct BlockCache {
             probes++;
             if (keyed) table[slot] = (key << 24) | (p < 0 ? 0xFFFFFFull : (unsigned long long)(uint32_t)p);
         }
-#if BF_RENDER_CACHE == 2
-        const bool toB = replaceB;
-        bx = toB ? b.x : bx; by = toB ? b.y : by; bz = toB ? b.z : bz; bp = toB ? p : bp;
-        ax = toB ? ax : b.x; ay = toB ? ay : b.y; az = toB ? az : b.z; ap = toB ? ap : p;
-        replaceB = !replaceB;
-#else
         ax = b.x; ay = b.y; az = b.z; ap = p;
-#endif
         return p;
     }
 };
@@ -596,11 +573,9 @@ __device__ __forceinline__ void render_pixel(const RayArgs& R, const BFRayCastPa
 // per-thread block cache holds one block (the sample's own corners no longer need two: trilinear resolves them
 // per sample) and the two pointers it spills are reloaded once per pixel. useGradients renders take the kernel
 // instantiated with the gradient path (its six extra samples need 17 more VGPRs).
-#ifndef BF_RENDER_WPE  // A/B builds: waves per SIMD asked of the compiler for the kernel without gradients
-#define BF_RENDER_WPE 5
-#endif
+constexpr int kRenderWpe = 5;  // waves per SIMD asked of the compiler for the kernel without gradients
 template <int TPB, bool GRAD>
-__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(GRAD ? 4 : BF_RENDER_WPE))) void k_render(RayArgs R, BFRayCastParams rp, const uint32_t* __restrict__ smin,
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(GRAD ? 4 : kRenderWpe))) void k_render(RayArgs R, BFRayCastParams rp, const uint32_t* __restrict__ smin,
                                                 const uint32_t* __restrict__ smax, float* d_depth, float4* d_depth4,
                                                 float4* d_normals, float4* d_colors, float* outMin, float* outMax,
                                                 unsigned long long* stats) {

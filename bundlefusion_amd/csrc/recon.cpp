@@ -1173,9 +1173,6 @@ void Recon::preprocessFrame(uint32_t f) {
     // voxel pass of frame f's batch
     recordInputs(f, ps);
     fr.pre = true;
-#ifdef BF_PRE_EARLY_WAIT  // A/B build: the scene stream waits right away (the first form)
-    awaitPreproc(f);
-#endif
     // copyToBundling: the cache takes the sensor-size raw depth and colour (as the FriedLiver app does)
     fr.srcDepth = preproc_->rawDepth();
     fr.srcColor = fr.rawColor;

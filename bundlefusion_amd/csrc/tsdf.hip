@@ -739,15 +739,8 @@ __global__ __launch_bounds__(256) void k_alloc_collect(HashArgs A, const float* 
 // the global dedup of k_alloc_insert removes blocks several ops want)
 // waves per SIMD asked of the compiler for the batched walk: 8 (63 VGPRs, 78 SGPRs with 65 spilled to VGPR lanes)
 // against its own choice of 7 (SGPR-limited): k_alloc_collect_ops 90 -> 86.5 us per frame (gpurun_out/s21)
-#ifndef BF_ALLOC_WPE
-#define BF_ALLOC_WPE 8
-#endif
-#if BF_ALLOC_WPE
-#define BF_ALLOC_ATTR __attribute__((amdgpu_waves_per_eu(BF_ALLOC_WPE)))
-#else
-#define BF_ALLOC_ATTR
-#endif
-__global__ __launch_bounds__(256) BF_ALLOC_ATTR void k_alloc_collect_ops(HashArgs A, BFDepthCameraParams cam, OpTable ops,
+constexpr int kAllocWpe = 8;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAllocWpe))) void k_alloc_collect_ops(HashArgs A, BFDepthCameraParams cam, OpTable ops,
                                                            unsigned long long* __restrict__ cand, uint32_t candCap,
                                                            uint8_t* __restrict__ candOp) {
     const uint32_t k = ops.intIdx[blockIdx.z];
@@ -1046,16 +1039,13 @@ __device__ __forceinline__ uint32_t blend_color(uint32_t c, uint32_t col, bool e
     return blend_channel(c & 0xFF, col & 0xFF, empty) | (blend_channel((c >> 8) & 0xFF, (col >> 8) & 0xFF, empty) << 8) |
            (blend_channel((c >> 16) & 0xFF, (col >> 16) & 0xFF, empty) << 16) | (255u << 24);
 }
-// blend_color with packed FP32 arithmetic (the batch pass; BF_BLEND_F=0 builds the integer form:
-// 4 VALU fewer per integrate update, k_apply_ops 619 / 618 -> 593 / 596 us, A/B pairs in
+// blend_color with packed FP32 arithmetic (the batch pass: 4 VALU fewer per integrate update than the
+// integer form, k_apply_ops 619 / 618 -> 593 / 596 us, A/B pairs in
 // profiles/r5_apply_experiments.txt): (cu + 4 oc) / 5 as (4 oc + cu)
 // x 0.2f (operands exact integers, product within 1e-5 of the quotient, whose fraction is a multiple of
 // 0.2), rounded by rintf (never a tie), min 254, and packed by v_cvt_pk_u8_f32 (an exact conversion of
 // an integral value). An empty voxel takes oc = cu, for which the quotient is cu. Same bytes as
 // blend_color for every (cu, oc, empty).
-#ifndef BF_BLEND_F
-#define BF_BLEND_F 1
-#endif
 __device__ __forceinline__ uint32_t blend_color_f(uint32_t c, uint32_t col, bool empty) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const uint32_t o = empty ? c : col;
@@ -1314,23 +1304,15 @@ constexpr uint32_t DC_DEPTH_KEY = 0xFF800000u;
 
 // k_apply_ops's grid: rounds of resident workgroups (Scene::Scene)
 constexpr int kApplyRounds = 4;
-// k_apply_ops's inner step and occupancy (overridable for A/B builds of kernel variants)
-#ifndef BF_APPLY_ZC
-#define BF_APPLY_ZC 4
-#endif
-#ifndef BF_APPLY_WPE
-#define BF_APPLY_WPE 8
-#endif
-// k_apply_ops: wave priority while a wave projects an op step's voxels and issues its gathers (0: off;
-// see apply_op_slices)
-#ifndef BF_APPLY_PRIO
-#define BF_APPLY_PRIO 1
-#endif
+// k_apply_ops's inner step (z slices per op step) and occupancy (waves per SIMD)
+constexpr int kApplyZc = 4;
+constexpr int kApplyWpe = 8;
+// k_apply_ops: wave priority while a wave projects an op step's voxels and issues its gathers (see
+// apply_op_slices)
+constexpr int kApplyPrio = 1;
 // k_compactify_ops: workgroups per CU, its occupancy (5: <= 96 VGPRs; 4 / 6 measured 49.0 / 47.1 us
 // against 44.7, profiles/r11_scan_ab.txt)
-#ifndef BF_SCAN_WPC
-#define BF_SCAN_WPC 5
-#endif
+constexpr int kScanWpc = 5;
 // work-list op mask of a block: which ops may update each z-half (x: voxel z 0..3, y: 4..7)
 typedef uint2 OpMask;
 constexpr int MASK_PARTS = 2;
@@ -1376,7 +1358,7 @@ __global__ __launch_bounds__(256) void k_begin_ops_tiles(uint32_t* ctrl, unsigne
 // One scan of the allocated pool for the whole batch: `visible` = frustum list of the last op (the
 // list garbageCollect walks), work list = blocks some op may update, with the op bit mask. Also
 // releases the batch's alloc dedup-set slots.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF_SCAN_WPC))) void k_compactify_ops(HashArgs A, BFDepthCameraParams cam, OpTable ops, uint32_t candCap,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kScanWpc))) void k_compactify_ops(HashArgs A, BFDepthCameraParams cam, OpTable ops, uint32_t candCap,
                                                         const int* __restrict__ candSlot, unsigned long long* candSet,
                                                         OpMask* masks, const uint32_t* __restrict__ birth, uint32_t epoch,
                                                         uint32_t binCap) {
@@ -1446,15 +1428,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF_SCAN_WPC
             const uint32_t e = s_q[wv][r], src = wv * 64 + (e >> 5), k = e & 31u;
             const int4 b = s_bp[src];
             // the voxel pass applies an op to a block half by half (4 z-slices per round)
-#if defined(BF_CULL_DIAG_NOBAND)  // timing diagnostic only (wrong masks): the scan without the band cull
-            const uint32_t hb = 3u;
-            (void)b;
-#else
             float cq[CULL_CONSTS];
 #pragma unroll
             for (int c = 0; c < CULL_CONSTS / 4; c++) reinterpret_cast<float4*>(cq)[c] = s_cull[k][c];
             const uint32_t hb = block_may_update_halves_q(A, cam, cq, b.x, b.y, b.z, s_tiles[0][k], s_tiles[1][k]);
-#endif
 #pragma unroll
             for (int q = 0; q < MASK_PARTS; q++)
                 if ((hb >> q) & 1u) atomicOr(&s_mask[q][src], 1u << k);
@@ -1529,20 +1506,11 @@ __device__ __forceinline__ bool work_slot(const uint32_t* ctrl, WorkCursor& c, u
     slot = (size_t)c.bin * binCap + (g - c.lo);
     return true;
 }
-// k_apply_ops, the batch's voxel pass: one wave per work-list block, lane = (x, y) column. The lane's
-// voxels of ZR z-slices stay in registers while the ops of the block's mask run over them in sequence
-// order (the outer loop), ZC z-slices per step (the inner one): project, gather {depth, colour}, band
-// test, then the integrate / de-integrate update of integrateDepthMapKernel (CUDASceneRepHashSDF.cu:
-// 420-521) on the register copy; each touched voxel is stored once. An op's z-slices project to nearly
-// the same pixels, so its gathers follow each other and hit the lines the previous slice fetched (the
-// z-round-outer order re-fetched every op's footprint once per round: 888 -> 856 us per launch at the
-// bench workload); the op's pose and the (x, y) part of its projection are taken once per ZR slices.
-// ZR = 4, ZC = 4 at 8 waves per SIMD (64 VGPRs; measured: ZR 4 / ZC 2 847 us, 7 waves 901 us).
 // Voxel updates of the batch pass (integrateDepthMapKernel, :467-514, weightUpdate = 1) on register
 // copies, for in-band voxels (sdf unclamped: see above). Weights are non-negative floats here, whose
 // bit patterns order like the values: min(1 + w, weightMax) is an integer min of the bits.
 __device__ __forceinline__ void batch_integrate(float& s0, float& w0, uint32_t& col, float sdf, uint32_t c, float weightMax) {
-    col = BF_BLEND_F ? blend_color_f(c, col, w0 == 0.0f) : blend_color(c, col, w0 == 0.0f);
+    col = blend_color_f(c, col, w0 == 0.0f);
     s0 = div_weight(sdf * 1.0f + s0 * w0, 1.0f + w0);
     w0 = __uint_as_float(min(__float_as_uint(1.0f + w0), __float_as_uint(weightMax)));
 }
@@ -1569,23 +1537,16 @@ struct RegVox {
 template <int ZR, int ZC, int TOFF = 0>
 __device__ __forceinline__ void apply_op_slices(bool deint, const HashArgs& A, const BFDepthCameraParams& cam, const BFMat4& Ti,
                                                 const float* bxy, __amdgpu_buffer_rsrc_t dcRsrc, uint32_t wc, float epsc,
-                                                int bzh, RegVox* rv, uint32_t& touched,
-                                                uint32_t& nupd, uint32_t& nwav
-#ifdef BF_APPLY_DIAG
-                                                , uint32_t* diag
-#endif
-                                                ) {
+                                                int bzh, RegVox* rv, uint32_t& touched, uint32_t& nupd) {
 #pragma unroll
     for (int z0 = 0; z0 < ZR; z0 += ZC) {
         uint32_t pix[ZC], cc[ZC];
         float pz[ZC], d[ZC];
-#if BF_APPLY_PRIO
         // the projection at a raised priority, back to normal once the step's gathers are issued: among the
         // SIMD's waves, one that is about to issue loads goes first, so more gathers are in flight while the
         // others run their updates (458 -> 441 us per launch; the raise over the whole kernel, above the
         // bundling kernels' waves, or for the update phase instead measured slower, profiles/r11_prio_ab.txt)
-        __builtin_amdgcn_s_setprio(BF_APPLY_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(kApplyPrio);
 #pragma unroll
         for (int zi = 0; zi < ZC; zi += 2) {
             const f2v wz = f2v{(float)(bzh + z0 + zi), (float)(bzh + z0 + zi + 1)} * f2v{A.voxelSize, A.voxelSize};
@@ -1601,39 +1562,15 @@ __device__ __forceinline__ void apply_op_slices(bool deint, const HashArgs& A, c
             d[zi] = __uint_as_float(v[0] ^ DC_DEPTH_KEY);
             cc[zi] = v[1];
         }
-#if BF_APPLY_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef BF_APPLY_DIAG
-        {  // (slice pair, op) wave-slots with no lane in band, and all of them (counted on lane 0)
-            unsigned long long b[ZC];
-#pragma unroll
-            for (int zi = 0; zi < ZC; zi++) b[zi] = __builtin_amdgcn_ballot_w64(fabsf(d[zi] - pz[zi]) < A.truncation + A.truncScale * d[zi]);
-            if (lane_id_here() == 0)
-#pragma unroll
-                for (int zi = 0; zi < ZC; zi += 2) { diag[4] += (b[zi] | b[zi + 1]) == 0; diag[5] += 1; }
-        }
-#endif
 #pragma unroll
         for (int zi = 0; zi < ZC; zi++) {
             const float sd = d[zi] - pz[zi];
             const float tr = A.truncation + A.truncScale * d[zi];
             const bool in = fabsf(sd) < tr;
-#ifdef BF_APPLY_DIAG
-            {  // measurement build: where the evaluations go (per lane)
-                const bool off = pix[zi] == 0xFFFFFFFFu, inval = !off && d[zi] == -INFINITY;
-                diag[0] += off;
-                diag[1] += inval;
-                diag[2] += !off && !inval && sd >= tr;
-                diag[3] += !off && !inval && sd <= -tr;
-            }
-#endif
             // the wave's in-band lanes, counted in uniform control flow (a scalar add inside the
             // divergent branch below would be per lane)
             nupd += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(in));
-#ifdef BF_APPLY_COUNT_WAVES
-            nwav += __builtin_amdgcn_ballot_w64(in) ? 64u : 0u;  // measurement build: update executions x 64 as voxels_rmw
-#endif
             if (!in) continue;
             touched |= 1u << (TOFF + z0 + zi);
             RegVox& v = rv[z0 + zi];
@@ -1652,12 +1589,13 @@ __device__ __forceinline__ void apply_op_slices(bool deint, const HashArgs& A, c
 // z-round-outer order re-fetched every op's footprint once per round: 888 -> 856 us per launch at the
 // bench workload); the op's pose and the (x, y) part of its projection are taken once per ZR slices.
 // ZR = 4, ZC = 4 at 8 waves per SIMD (64 VGPRs; measured: ZR 4 / ZC 2 847 us, 7 waves 901 us). One wave
-// per workgroup (a slot is handed on as soon as its wave ends). The kernel sits at neither roof: ~0.5 of the
-// VALU issue peak and 0.36 of HBM by the counters at the driver workload (458-461 us per launch), with the
-// waves' cycles 22 % issuing, 45.5 % waiting to issue (dependencies) and 32.5 % waiting on memory
-// (profiles/r10_apply_sq_pmc.txt): it is dependency / latency bound. Lane-derived values are re-read per
-// block instead of kept live (no spills), counters are scalar. The op steps' projections run at a raised
-// issue priority (apply_op_slices): 458 -> 441 us.
+// per workgroup (a slot is handed on as soon as its wave ends). The kernel sits at neither roof: in round 5
+// (458-461 us per launch at the driver workload) ~0.5 of the VALU issue peak and 0.36 of HBM by the counters
+// (profiles/r10_apply_sq_pmc.txt); in round 6, at 435 us, the waves' cycles 23.4 % issuing, 46.0 % waiting to
+// issue (dependencies) and 30.6 % waiting on memory (profiles/r11_apply_sq_pmc.txt): it is dependency /
+// latency bound. Lane-derived values are re-read per block instead of kept live (no spills), counters are
+// scalar. The op steps' projections run at a raised issue priority (apply_op_slices): 458 -> 441 us; the next
+// block's entry is loaded ahead: 440 -> 435 us (profiles/r11_prio_ab.txt).
 template <int ZR, int ZC, int WPE, bool XCDRUNS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_apply_ops(
     HashArgs A, BFDepthCameraParams cam, OpTable ops, const OpMask* __restrict__ masks, const int4* __restrict__ band, uint32_t binCap,
@@ -1677,9 +1615,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     }
     const float epsc = (3.0f * (float)(max(cam.imageWidth, cam.imageHeight) + 2u) + fmaxf(fabsf(cam.mx), fabsf(cam.my)) + 3.0f) * 0x1p-21f;
     uint32_t updated = 0, rmw = 0, halves = 0;  // per wave and launch: < 2^32
-#ifdef BF_APPLY_DIAG
-    uint32_t diag[6] = {0, 0, 0, 0, 0, 0}, diagPairs = 0, diagEmpty = 0;
-#endif
     WorkCursor cur = work_begin(A.ctrl, ops.n);
     size_t b;
     auto pos = [&](uint32_t v) { return XCDRUNS ? (((v >> xcdShift) << 3 | xcd) << xcdShift) | (v & cmask) : v; };
@@ -1706,7 +1641,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         const float wx = (float)bx * A.voxelSize, wy = (float)by * A.voxelSize;
         Vox3* vp = reinterpret_cast<Vox3*>(A.voxels + (size_t)e.w * BF_VOXELS_PER_BLOCK) + lane;
         int dcount = 0;
-        uint32_t nupd = 0, nrmw = 0, nwav = 0;
+        uint32_t nupd = 0, nrmw = 0;
 #pragma unroll
         for (int h = 0; h < BF_SDF_BLOCK_SIZE; h += ZR) {
             // a half no op reaches is neither read nor written (wave-uniform branch on an SGPR mask)
@@ -1731,14 +1666,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                 const int dcBytes = (int)(cam.imageWidth * cam.imageHeight * 8u);
                 const __amdgpu_buffer_rsrc_t dcRsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ops.dc[k], (short)0, dcBytes, 0x00020000);
                 const uint32_t wc = ops.color[k] != nullptr ? cam.imageWidth : 0u;
-#ifdef BF_APPLY_DIAG
-                const uint32_t before = nupd;
-                apply_op_slices<ZR, ZC>((ops.deintMask >> k) & 1u, A, cam, Ti, bxy, dcRsrc, wc, epsc, bz + h, rv, touched, nupd, nwav, diag);
-                diagPairs++;
-                diagEmpty += nupd == before;
-#else
-                apply_op_slices<ZR, ZC>((ops.deintMask >> k) & 1u, A, cam, Ti, bxy, dcRsrc, wc, epsc, bz + h, rv, touched, nupd, nwav);
-#endif
+                apply_op_slices<ZR, ZC>((ops.deintMask >> k) & 1u, A, cam, Ti, bxy, dcRsrc, wc, epsc, bz + h, rv, touched, nupd);
             }
 #pragma unroll
             for (int z = 0; z < ZR; z++) {
@@ -1757,11 +1685,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             if (lane_id_here() == 0 && total != 0) atomicAdd(&A.blockCount[blk], (uint32_t)total);
         }
         updated += nupd;
-#ifdef BF_APPLY_COUNT_WAVES
-        rmw += lane_id_here() == 0 ? nwav : 0u;
-#else
         rmw += nrmw;
-#endif
     }
     // updated is the wave's total (scalar), rmw per lane; one wave per workgroup: its sums go straight to the
     // workgroup's counter slot (no LDS stage, no barriers)
@@ -1780,16 +1704,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             if (halves) atomicAdd(&st[S_BHALF], (unsigned long long)halves);
         }
     }
-#ifdef BF_APPLY_DIAG
-    __syncthreads();
-    flush_stats2(A.stats, 20, diag[0], 21, diag[1]);
-    __syncthreads();
-    flush_stats2(A.stats, 22, diag[2], 23, diag[3]);
-    __syncthreads();
-    flush_stats2(A.stats, 24, lane_id_here() == 0 ? diagPairs : 0u, 25, lane_id_here() == 0 ? diagEmpty : 0u);
-    __syncthreads();
-    flush_stats2(A.stats, 26, diag[4], 27, diag[5]);
-#endif
 }
 
 __device__ void gc_free_list_serial(const HashArgs& A, unsigned long long* listV, uint32_t* locked);
@@ -1950,11 +1864,7 @@ __device__ void gc_free_list_serial(const HashArgs& A, unsigned long long* listV
 
 // ------------------------------------------------------------------------------------
 // RN(1 / x) for the divisors div_by_uniform admits ([2^-20, 2^20]), else 0 (the kernels divide in IEEE)
-// (BF_ALLOC_UNIFORM_DIV=0 builds the IEEE-only walk setup, for A/B and for the fallback's parity)
-#ifndef BF_ALLOC_UNIFORM_DIV
-#define BF_ALLOC_UNIFORM_DIV 1
-#endif
-static float recip_or_zero(float x) { return (BF_ALLOC_UNIFORM_DIV && x >= 0x1p-20f && x <= 0x1p20f) ? 1.0f / x : 0.0f; }
+static float recip_or_zero(float x) { return (x >= 0x1p-20f && x <= 0x1p20f) ? 1.0f / x : 0.0f; }
 static void set_camera_recips(HashArgs& a, const BFDepthCameraParams& cam) {
     const float rx = recip_or_zero(cam.fx), ry = recip_or_zero(cam.fy);
     a.rFx = (rx != 0.0f && ry != 0.0f) ? rx : 0.0f;
@@ -2056,7 +1966,7 @@ Scene::Scene(const SceneConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(st
     // pass counter flush waited for all four): k_apply_ops 475-477 -> 466-467 us, 1 484-1 487 -> 1 498-1 499
     // frames/s at the bench workload, config 4's stream and the G = 8 rehearsal unchanged
     // (profiles/r10_apply_tpb_ab.txt).
-    BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occA, k_apply_ops<4, BF_APPLY_ZC, BF_APPLY_WPE, true>, 64, 0));
+    BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occA, k_apply_ops<4, kApplyZc, kApplyWpe, true>, 64, 0));
     // sharded: one 256-thread workgroup's worth of slots per CU stays free for the bundling streams' launches
     const int freeSlots = cfg_.shardCount > 1 ? 4 : 0;
     // The grid is applyRounds (4) rounds of resident workgroups, each wave a 1/applyRounds share of the strided
@@ -2075,8 +1985,9 @@ Scene::Scene(const SceneConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(st
     applyXcdShift_ = -1;
     for (int sh = 0; sh < 16; sh++)
         if (run == (1u << sh)) applyXcdShift_ = sh;
-    // the batch scan: 4 workgroups per CU (its occupancy; 5-6 per CU and 2-3 resident rounds measured no faster)
-    compactifyGrid_ = (unsigned)numCUs_ * (unsigned)BF_SCAN_WPC;
+    // the batch scan: 5 workgroups per CU, its occupancy (kScanWpc; 4 / 6 per CU measured slower,
+    // profiles/r11_scan_ab.txt)
+    compactifyGrid_ = (unsigned)numCUs_ * (unsigned)kScanWpc;
     integrateGrid_[0] = (unsigned)std::max(1, occ0) * (unsigned)numCUs_;
     integrateGrid_[1] = (unsigned)std::max(1, occ1) * (unsigned)numCUs_;
     BF_HIP(hipMemsetAsync(candSet_.p, 0xFF, candSet_.bytes(), stream_));
@@ -2301,11 +2212,11 @@ void Scene::applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const bool timed = applyClock_.enabled() && applyClock_.slotSampled(ev0, ev1);
     if (applyGrid_ % 8u == 0u)  // workgroup i runs on XCD i mod 8
-        hipExtLaunchKernelGGL(k_apply_ops<4, BF_APPLY_ZC, BF_APPLY_WPE, true>, dim3(applyGrid_), dim3(64), 0, stream_, ev0, ev1, 0, A,
+        hipExtLaunchKernelGGL(k_apply_ops<4, kApplyZc, kApplyWpe, true>, dim3(applyGrid_), dim3(64), 0, stream_, ev0, ev1, 0, A,
                               cam, tab, reinterpret_cast<const OpMask*>(blockMask_.p), static_cast<const int4*>(band_.p), B_,
                               applyXcdShift_);
     else
-        hipExtLaunchKernelGGL(k_apply_ops<4, BF_APPLY_ZC, BF_APPLY_WPE, false>, dim3(applyGrid_), dim3(64), 0, stream_, ev0, ev1, 0, A,
+        hipExtLaunchKernelGGL(k_apply_ops<4, kApplyZc, kApplyWpe, false>, dim3(applyGrid_), dim3(64), 0, stream_, ev0, ev1, 0, A,
                               cam, tab, reinterpret_cast<const OpMask*>(blockMask_.p), static_cast<const int4*>(band_.p), B_, -1);
     BF_LAUNCH_CHECK();
     if (timed) applyClock_.commit();
@@ -2363,11 +2274,6 @@ BFTsdfStats Scene::stats() {
     static_assert(sizeof(BFTsdfStats) == 18 * 8 && sizeof(BFTsdfStats) <= STAT_FIELDS * 8, "stats layout");
     std::memcpy(&s, sum, sizeof(s));
     s.pixels += hostPixels_;
-#ifdef BF_APPLY_DIAG
-    fprintf(stderr, "apply diag: offscreen %llu invalid %llu front %llu behind %llu (half,op) pairs %llu empty %llu (slice pair,op) %llu empty %llu\n",
-            (unsigned long long)sum[20], (unsigned long long)sum[21], (unsigned long long)sum[22], (unsigned long long)sum[23],
-            (unsigned long long)sum[24], (unsigned long long)sum[25], (unsigned long long)sum[27], (unsigned long long)sum[26]);
-#endif
     return s;
 }
 
