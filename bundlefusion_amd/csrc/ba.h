@@ -19,6 +19,9 @@
 // A solve is enqueued asynchronously on the solver's stream: PCG early exit and GN convergence
 // are evaluated on the device, so there is no host round trip inside solve (the reference
 // copies scanAlpha to the host every PCG iteration, SolverBundling.cu:1089).
+//
+// Source layout: ba.hip is the one translation unit (Solver's host code, the pose and gate kernels);
+// the solve's kernels are in the ba_*.h headers that only it includes, one per route (listed in ba.hip).
 #pragma once
 #include <vector>
 #include "../../include/bf/bf.h"
@@ -105,13 +108,12 @@ struct SolveResult {
 };
 
 namespace {
-struct BA;  // the kernels' argument block: local to ba.hip, named here for Solver's private members
+struct BA;  // the kernels' argument block (ba_dev.h): local to ba.hip, named here for Solver's private members
 }
 
 class Solver {
 public:
     Solver(const SolverConfig& cfg, hipStream_t stream);
-    ~Solver();
     void solve(const SolveArgs& a);       // async
     SolveResult result();                 // synchronizes
     // async variants for the reconstruction loop: copy the result words into pinned host memory
@@ -133,12 +135,11 @@ public:
     // moves the solver's later work to another stream (the caller orders it after this one's)
     void setStream(hipStream_t s) { stream_ = s; }
     const SolverConfig& config() const { return cfg_; }
-    size_t deviceBytes() const;
     // sharded global solve: this handle builds the normal-equation blocks of the
     // image pairs p with p % count == index; comm (may be null: no exchange, tests) sums them
     void setShard(uint32_t count, uint32_t index, Comm* comm);
     // assembled normal equations of the last GN iteration: per pair (a, b) the 28 sufficient
-    // statistics (see ba.hip, k_pair_stats); synchronizes
+    // statistics (see ba_table.h, k_pair_stats); synchronizes
     uint32_t exportPairs(double* stats, int* pairAB, uint32_t cap);
     KernelClock& solveClock() { return solveClock_; }  // whole-solve device time (ms/GN-iter)
     KernelClock& pcgClock() { return pcgClock_; }      // device time of the persistent PCG launches

@@ -28,7 +28,6 @@ BFMat4 mat4_inverse(const BFMat4& M);  // api.cpp
 
 namespace {
 
-const float MINF_F = -__builtin_inff();
 enum RenderStat { RS_SAMPLES = 0, RS_LOADS, RS_PROBES, RS_RAYS, RS_QUADS, RS_ATOMICS, RS_RENDERS, RS_PIXELS, RS_WAVESAMPLES, RS_WAVEMAX, RS_LONGWAVES, RS_COUNT };
 
 static_assert(RS_COUNT <= Scene::kRenderStatFields, "render counters per slot");

@@ -916,19 +916,6 @@ __device__ void alloc_overflow_serial(const HashArgs& A, const unsigned long lon
     }
 }
 
-__global__ void k_alloc_overflow(HashArgs A, const unsigned long long* ovf) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    alloc_overflow_serial(A, ovf);
-}
-
-__global__ void k_alloc_cleanup(const uint32_t* ctrl, uint32_t candCap, const int* candSlot, unsigned long long* candSet) {
-    const uint32_t n = min(ctrl[C_CAND], candCap);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int s = candSlot[i];
-        if (s >= 0) candSet[s] = EMPTY_KEY;
-    }
-}
-
 // compactifyHashAllInOneKernel, CUDASceneRepHashSDF.cu:324-366: stream the allocated pool
 // prefix [0, highWater), keep the in-frustum blocks; wave ballot + one atomic per wave.
 enum CompactMode { CM_FRUSTUM = 0, CM_INTEGRATE = 1 };
@@ -1056,26 +1043,6 @@ __device__ __forceinline__ uint32_t blend_color_f(uint32_t c, uint32_t col, bool
     r = __builtin_amdgcn_cvt_pk_u8_f32(fminf(rintf(t.y), 254.0f), 1u, r);
     return __builtin_amdgcn_cvt_pk_u8_f32(fminf(rintf(t2), 254.0f), 2u, r);
 }
-// Voxel update of integrateDepthMapKernel (CUDASceneRepHashSDF.cu:486-514), weightUpdate = 1.
-__device__ __forceinline__ void voxel_integrate(float& s0, float& w0, uint32_t& col, float sdf, uint32_t c, float weightMax) {
-    const float wUpd = 1.0f;
-    col = blend_color(c, col, w0 == 0.0f);
-    s0 = (sdf * wUpd + s0 * w0) / (wUpd + w0);
-    w0 = fminf(weightMax, wUpd + w0);
-}
-__device__ __forceinline__ void voxel_deintegrate(float& s0, float& w0, uint32_t& col, float sdf, uint32_t c) {
-    const float wUpd = 1.0f;
-    const float cu0 = (float)(c & 0xFF), cu1 = (float)((c >> 8) & 0xFF), cu2 = (float)((c >> 16) & 0xFF);
-    const float oc0 = (float)(col & 0xFF), oc1 = (float)((col >> 8) & 0xFF), oc2 = (float)((col >> 16) & 0xFF);
-    const float den = w0 - wUpd, rden = __builtin_amdgcn_rcpf(den);
-    float r0 = fmaxf(0.0f, fminf(round_quot(oc0 * w0 - cu0 * wUpd, den, rden), 254.5f));
-    float r1 = fmaxf(0.0f, fminf(round_quot(oc1 * w0 - cu1 * wUpd, den, rden), 254.5f));
-    float r2 = fmaxf(0.0f, fminf(round_quot(oc2 * w0 - cu2 * wUpd, den, rden), 254.5f));
-    col = (uint32_t)(uint8_t)r0 | ((uint32_t)(uint8_t)r1 << 8) | ((uint32_t)(uint8_t)r2 << 16) | (255u << 24);
-    s0 = (s0 * w0 - sdf * wUpd) / (w0 - wUpd);
-    w0 = fmaxf(0.0f, w0 - wUpd);
-    if (w0 <= 0.001f) { s0 = 0.0f; col = 0u; w0 = 0.0f; }
-}
 
 // The running-average quotient num / den of the voxel update, den = an integral weight in [0, 1024]:
 // rcp, product, one fma residual and one fma correction. Checked bit-identical to the IEEE division
@@ -1087,11 +1054,6 @@ __device__ __forceinline__ float div_weight(float num, float den) {
     const float q = num * r;
     const float e = __builtin_fmaf(-q, den, num);
     return __builtin_fmaf(e, r, q);
-}
-__device__ __forceinline__ void voxel_integrate_f(float& s0, float& w0, uint32_t& col, float sdf, uint32_t c, float weightMax) {
-    col = blend_color(c, col, w0 == 0.0f);
-    s0 = div_weight(sdf * 1.0f + s0 * w0, 1.0f + w0);
-    w0 = fminf(weightMax, 1.0f + w0);
 }
 // De-integrate colour of one channel, u8(clamp(roundf((oc w - cu) / (w - 1)), 0, 254.5)), for an
 // integral weight w >= 2 (every weight the update produces: +-1 steps from 0, capped by the integral
@@ -1176,15 +1138,6 @@ __device__ __forceinline__ void voxel_pixel2b(const BFDepthCameraParams& cam, co
     pz = p[2];
     off0 = ((ux0 < wc) & (uy0 < cam.imageHeight)) ? __umul24(uy0, W8) + (ux0 << 3) : 0xFFFFFFFFu;
     off1 = ((ux1 < wc) & (uy1 < cam.imageHeight)) ? __umul24(uy1, W8) + (ux1 << 3) : 0xFFFFFFFFu;
-}
-
-// Band test of one voxel for one pose (CUDASceneRepHashSDF.cu:449-466): sdf clamped to +-truncation.
-__device__ __forceinline__ bool voxel_in_band(const HashArgs& A, float dz, float pz, float& sdf) {
-    sdf = dz - pz;
-    const float tr = A.truncation + A.truncScale * dz;
-    const bool in = dz != -INFINITY && dz < A.maxIntegrationDistance && fabsf(sdf) < tr;
-    sdf = (sdf >= 0.0f) ? fminf(tr, sdf) : fmaxf(-tr, sdf);
-    return in;
 }
 
 // integrateDepthMapKernel<deIntegrate>, CUDASceneRepHashSDF.cu:420-521. One wave per block:

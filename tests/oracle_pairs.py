@@ -1,6 +1,6 @@
 """Test infrastructure (checker only): numpy restatement of the bundle adjuster's sparse operator in
-its two forms, used to pin the assembled (per image pair) normal equations of csrc/ba.hip against the
-reference's matrix-free products.
+its two forms, used to pin the assembled (per image pair) normal equations of csrc/ba_table.h and
+csrc/ba_pcg.h against the reference's matrix-free products.
 
 matrix_free_*: applyJDevice / applyJTDevice and evalMinusJTFDevice
     (Source/Solver/SolverBundlingEquationsLie.h:63-148, :154-228): per correspondence c = (i, j),

@@ -1,5 +1,5 @@
 """CPU checks of the assembled (per image pair) normal equations used by the global solve
-(csrc/ba.hip k_pair_stats / k_pair_init / k_pcg_pairs): the operator and right-hand side rebuilt
+(csrc/ba_table.h k_pair_stats, csrc/ba_pcg.h k_pair_init / k_pcg_pairs): the operator and right-hand side rebuilt
 from the 28 per-pair statistics equal the reference's matrix-free J^T J p and J^T F
 (SolverBundlingEquationsLie.h:63-228) on seeded problems with outliers."""
 import numpy as np
