@@ -18,7 +18,7 @@ from .abi import (BFDepthCameraParams, BFHashParams, BFMarchingCubesParams, BFRa
 
 __all__ = ["lib", "BFError", "DeviceArray", "SceneRepHashSDF", "hash_params", "depth_camera",
            "synth_scene", "synth_pose", "synth_render", "synth_render_host", "mc_params", "mesh_merge", "mesh_save_ply",
-           "Matcher", "matcher_options", "CacheFrames", "match_verify_options"]
+           "Matcher", "matcher_options", "CacheFrames", "match_verify_options", "Sift", "sift_options"]
 
 _lib = None
 
@@ -376,8 +376,11 @@ def synth_render_host(scene: BFSynthScene, T, cam: BFDepthCameraParams, noise_se
     return d, c
 
 
-def __getattr__(name):  # the matcher binding imports this module's helpers, so it is resolved on first use
+def __getattr__(name):  # the matcher and detector bindings import this module's helpers: resolved on first use
     if name in ("Matcher", "matcher_options", "CacheFrames", "match_verify_options"):
         from . import match
         return getattr(match, name)
+    if name in ("Sift", "sift_options"):
+        from . import sift
+        return getattr(sift, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -235,10 +235,19 @@ class BFMatchVerifyOptions(C.Structure):  # include/bf/types.h: the surface-area
                 ("sensorDepthMax", C.c_float), ("reserved", C.c_uint32)]
 
 
+class BFSiftOptions(C.Structure):  # include/bf/types.h: the SIFT detector (bf_sift_*), 0 = default
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("depthWidth", C.c_uint32), ("depthHeight", C.c_uint32),
+                ("maxKeys", C.c_uint32), ("featureCountThreshold", C.c_uint32), ("sensorDepthMin", C.c_float),
+                ("sensorDepthMax", C.c_float), ("minKeyScale", C.c_float), ("dogThreshold", C.c_float),
+                ("edgeThreshold", C.c_float), ("reserved", C.c_uint32)]
+
+
+SIFT_LEVELS, SIFT_MAX_FILTER, SIFT_TRUNCATED = 12, 33, 1
 SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
 MAX_MATCHES_RAW, MAX_MATCHES_FILTERED, MATCH_MAX_KEYS_PER_IMAGE = 128, 25, 1024
 assert C.sizeof(BFSiftKeyPoint) == 16 and SIFT_KEYPOINT_DTYPE.itemsize == 16
 assert C.sizeof(BFMatchVerifyOptions) == 32
+assert C.sizeof(BFSiftOptions) == 48
 
 
 class BFVoxelOp(C.Structure):  # include/bf/bf.h

@@ -15,6 +15,7 @@
 #include "app.h"
 #include "frontend.h"
 #include "match.h"
+#include "sift.h"
 
 #include <cstring>
 #include <memory>
@@ -144,6 +145,11 @@ struct bf_matcher {
     Matcher* m = nullptr;
 };
 
+struct bf_sift {
+    hipStream_t stream = nullptr;
+    Sift* s = nullptr;
+};
+
 extern "C" {
 
 int bf_abi_version(void) { return BF_ABI_VERSION; }
@@ -171,6 +177,7 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFCorrOptions", sizeof(BFCorrOptions)},
         {"BFSiftKeyPoint", sizeof(BFSiftKeyPoint)},
         {"BFMatcherOptions", sizeof(BFMatcherOptions)},
+        {"BFSiftOptions", sizeof(BFSiftOptions)},
         {"BFMatchVerifyOptions", sizeof(BFMatchVerifyOptions)},
         {"BFCachedFrame", sizeof(BFCachedFrame)},
         {"BFSceneOptions", sizeof(BFSceneOptions)},
@@ -1381,6 +1388,102 @@ int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms) {
     BF_TRY
     BF_REQUIRE(m && t && ms, BF_ERR_ARG, "null argument");
     BF_HIP(hipEventRecord(t->b, m->stream));
+    BF_HIP(hipEventSynchronize(t->b));
+    BF_HIP(hipEventElapsedTime(ms, t->a, t->b));
+    BF_CATCH
+}
+
+// ---- SIFT detector (Bundler::detectFeatures -> SiftGPU::RunSIFT + GetKeyPointsAndDescriptorsCUDA) ------
+int bf_sift_create(const BFSiftOptions* opts, bf_sift** out) {
+    BF_TRY
+    BF_REQUIRE(opts && out, BF_ERR_ARG, "null argument");
+    *out = nullptr;
+    const SiftConfig cfg = make_sift_config(opts);  // option checks before any device work
+    bf_sift* h = new bf_sift();
+    try {
+        BF_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        h->s = new Sift(cfg, h->stream);
+    } catch (...) {
+        if (h->stream) (void)hipStreamDestroy(h->stream);
+        delete h;
+        throw;
+    }
+    *out = h;
+    BF_CATCH
+}
+int bf_sift_destroy(bf_sift* s) {
+    BF_TRY
+    if (s) {
+        if (s->stream) (void)hipStreamSynchronize(s->stream);
+        delete s->s;
+        if (s->stream) (void)hipStreamDestroy(s->stream);
+        delete s;
+    }
+    BF_CATCH
+}
+int bf_sift_intensity(bf_sift* s, const uint8_t* d_color, uint32_t colorWidth, uint32_t colorHeight, float* d_out) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->intensity(d_color, colorWidth, colorHeight, d_out);
+    BF_CATCH
+}
+int bf_sift_detect(bf_sift* s, const float* d_intensity, const float* d_depth) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->detect(d_intensity, d_depth);
+    BF_CATCH
+}
+int bf_sift_result(bf_sift* s, const BFSiftKeyPoint** d_keys, const uint8_t** d_descs, uint32_t* n, uint32_t* flags) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->result(d_keys, d_descs, n, flags);
+    BF_CATCH
+}
+int bf_sift_level_counts(bf_sift* s, uint32_t raw[12], uint32_t kept[12]) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->levelCounts(raw, kept);
+    BF_CATCH
+}
+int bf_sift_filter_kernel(bf_sift* s, uint32_t index, float k[33], uint32_t* width) {
+    BF_TRY
+    BF_REQUIRE(index < 6, BF_ERR_ARG, "filter index >= 6");
+    SiftTables local;
+    if (!s) make_sift_tables(local);  // the tables do not depend on the options
+    const SiftTables& t = s ? s->s->tables() : local;
+    if (k) std::memcpy(k, t.k[index], sizeof(float) * BF_SIFT_MAX_FILTER);
+    if (width) *width = t.width[index];
+    BF_CATCH
+}
+int bf_sift_debug_level(bf_sift* s, uint32_t octave, uint32_t level, float* host) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->debugLevel(octave, level, host);
+    BF_CATCH
+}
+int bf_sift_debug_raw_keys(bf_sift* s, uint32_t levelIndex, int32_t* colRow, uint32_t* packedOrientations, uint32_t cap,
+                           uint32_t* n) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    s->s->debugRawKeys(levelIndex, colRow, packedOrientations, cap, n);
+    BF_CATCH
+}
+int bf_sift_synchronize(bf_sift* s) {
+    BF_TRY
+    BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
+    BF_HIP(hipStreamSynchronize(s->stream));
+    BF_CATCH
+}
+int bf_sift_timer_start(bf_sift* s, bf_timer* t) {
+    BF_TRY
+    BF_REQUIRE(s && t, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->a, s->stream));
+    BF_CATCH
+}
+int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms) {
+    BF_TRY
+    BF_REQUIRE(s && t && ms, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->b, s->stream));
     BF_HIP(hipEventSynchronize(t->b));
     BF_HIP(hipEventElapsedTime(ms, t->a, t->b));
     BF_CATCH

@@ -30,7 +30,8 @@ extern "C" {
                              BFSceneCapacity + bf_scene_capacity / bf_recon_scene_capacity (scene errors fail the loop),
                              bf_recon_set_render (visualizeFrame's render per frame);
                              additive, still 4: the sparse matcher (BFSiftKeyPoint, BFMatcherOptions, bf_matcher_*);
-                             additive, still 4: its surface-area and dense-verify filters (BFMatchVerifyOptions, bf_match_*) */
+                             additive, still 4: its surface-area and dense-verify filters (BFMatchVerifyOptions, bf_match_*);
+                             additive, still 4: the SIFT detector (BFSiftOptions, bf_sift_*) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -605,8 +606,8 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
 
 /* ---- sparse matcher: the matching side of SIFTImageManager + SiftMatch + Bundler::matchAndFilter ----------
  * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out, through the reference's whole
- * filter chain: Kabsch, surface area, dense verify, filterFrames (the DoG detector / descriptor, tryRevalidation and
- * fuseToGlobal are not part of it).
+ * filter chain: Kabsch, surface area, dense verify, filterFrames (the DoG detector / descriptor is bf_sift_* below;
+ * tryRevalidation and fuseToGlobal are not part of it).
  * Work is queued on the matcher's own stream; the read-backs and bf_matcher_filter_frames / _add_to_residuals
  * wait for it. No device allocation after bf_matcher_create. Per-pair results are indexed by the earlier image
  * `prev`, as the reference's d_curr* arrays are, and hold the last bf_matcher_match / _filter.
@@ -709,6 +710,64 @@ int bf_match_debug_set_filtered(bf_matcher* m, uint32_t prev, uint32_t count, co
 int bf_matcher_synchronize(bf_matcher* m);
 int bf_matcher_timer_start(bf_matcher* m, bf_timer* t);
 int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms); /* synchronizes */
+
+/* ---- SIFT detector: Bundler::detectFeatures (Bundler.cpp:91-101) -> SiftGPU::RunSIFT + GetKeyPointsAndDescriptorsCUDA ---
+ * Float intensity + filtered float depth in, exactly what bf_matcher_add_image takes out: BFSiftKeyPoint[n] and uint8
+ * descriptors [n][128], DEVICE resident. The semantics are SiftGPU's as BundleFusion configures it (BFSiftOptions), not
+ * textbook SIFT: DESIGN.md §3.6 restates them stage by stage. Everything is queued on the detector's own stream with
+ * no host round trip: level counts, both LimitFeatureCount passes, the minKeyScale filter and the key cap are computed
+ * on the device, later kernels are launched with worst-case grids. Only bf_sift_result (and the read-backs) synchronize.
+ * No device allocation after bf_sift_create.
+ *
+ * Deliberate departures from the reference, all so that results are bit-deterministic:
+ *  1. A level's raw key list is in (row, col) ascending order and its cap keeps the first fmax of that order (the
+ *     reference appends at an atomic counter). Final keys are ordered by level index, then raw order; a key's second
+ *     orientation directly follows its first.
+ *  2. The orientation votes and descriptor bins are summed in a fixed order (the reference: shared-memory float
+ *     atomicAdd); __fdividef / __sincosf / rsqrt are the ordinary device division, sincosf and 1 / sqrtf.
+ *  3. Above maxKeys the coarsest levels are kept whole and the level that crosses the cap keeps its first keys in list
+ *     order, descriptors follow the same keys and BF_SIFT_TRUNCATED is reported (the reference tests bHasMax inverted,
+ *     SiftPyramid.cpp:748-757, and Bundler::detectFeatures throws).
+ * Level index = octave * 3 + DoG level, 0...11. */
+typedef struct bf_sift bf_sift;
+/* SiftGPU::SetParams + InitSiftGPU + SiftParam::ParseSiftParam (SiftGPU.cpp:127-253). Host checks first, each
+ * BF_ERR_ARG: null argument; width / height outside 32...4096 (octave 3 is (w >> 3) x (h >> 3) and the key test runs on
+ * rows and columns 1...dim - 3, so below 32 the coarsest octave has no pixel to test); depth size outside 1...4096;
+ * maxKeys outside 1...1024 (0 = 1024); a negative or non-finite threshold; sensorDepthMin > sensorDepthMax. */
+int bf_sift_create(const BFSiftOptions* opts, bf_sift** out);
+int bf_sift_destroy(bf_sift* s);
+/* CUDAImageUtil::resampleToIntensity (CUDAImageUtil.cu:197-248): DEVICE RGBX colour[colorHeight][colorWidth] (>= 2 x 2)
+ * -> float intensity at the detector's size, into d_out or, when NULL, the detector's own buffer. Asynchronous. */
+int bf_sift_intensity(bf_sift* s, const uint8_t* d_color, uint32_t colorWidth, uint32_t colorHeight, float* d_out);
+/* SiftPyramid::RunSIFT (SiftPyramid.cpp:148-224) + CreateGlobalKeyPointList + GetFeatureVectorCUDA: d_intensity DEVICE
+ * float[height][width] (NULL = the buffer bf_sift_intensity filled; BF_ERR_STATE if it never did), d_depth DEVICE
+ * float[depthHeight][depthWidth]
+ * (-inf or outside [sensorDepthMin, sensorDepthMax] = invalid). Asynchronous on the detector's stream; the inputs are
+ * read there: keep them until bf_sift_result / bf_sift_synchronize. */
+int bf_sift_detect(bf_sift* s, const float* d_intensity, const float* d_depth);
+/* The last detect's output: DEVICE keys[*n], DEVICE descriptors[*n][128], valid until the next bf_sift_detect; *flags
+ * = BF_SIFT_TRUNCATED or 0. Any output may be NULL. Synchronizes. */
+int bf_sift_result(bf_sift* s, const BFSiftKeyPoint** d_keys, const uint8_t** d_descs, uint32_t* n, uint32_t* flags);
+/* Per level of the last detect: raw = keys the key test found (before the per-level cap), kept = keys of the level in
+ * the output (after cap, both LimitFeatureCount passes, minKeyScale and maxKeys; second orientations count).
+ * HOST outputs, either may be NULL. Synchronizes. */
+int bf_sift_level_counts(bf_sift* s, uint32_t raw[12], uint32_t kept[12]);
+/* ProgramCU::CreateFilterKernel (ProgramCU.cu:431-460) of table `index` (0 = the initial smoothing, 1...5 = the level
+ * increments): k[33] (zero behind *width). Host tables built at create; touches no device. s may be NULL: the tables
+ * do not depend on the options. */
+int bf_sift_filter_kernel(bf_sift* s, uint32_t index, float k[33], uint32_t* width);
+/* test read-back: Gaussian level `level` (0...5) of octave `octave` (0...3) of the last detect, HOST float
+ * [(height >> octave)][(width >> octave)]. Synchronizes. */
+int bf_sift_debug_level(bf_sift* s, uint32_t octave, uint32_t level, float* host);
+/* test read-back of level levelIndex's raw list after the cap and LimitFeatureCount(0): *n keys, the first min(*n, cap)
+ * as colRow[2 * i] = {col, row} and packedOrientations[i] = second << 16 | first (ComputeOrientation_Kernel's packing,
+ * 65535 = none; 0xFFFFFFFF for a level that cannot pass minKeyScale, whose orientations are skipped). HOST outputs,
+ * any may be NULL. Synchronizes. */
+int bf_sift_debug_raw_keys(bf_sift* s, uint32_t levelIndex, int32_t* colRow, uint32_t* packedOrientations, uint32_t cap,
+                           uint32_t* n);
+int bf_sift_synchronize(bf_sift* s);
+int bf_sift_timer_start(bf_sift* s, bf_timer* t);
+int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
 
 /* ---- mesh output: CUDAMarchingCubesHashSDF::saveMesh (CUDAMarchingCubesHashSDF.cpp:48-105) ------
  * Triangle soup (HOST BFMcTriangle[n], e.g. from bf_scene_extract_mesh) -> indexed mesh as saveMesh

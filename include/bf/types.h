@@ -315,9 +315,29 @@ typedef struct BFMatchVerifyOptions {
     uint32_t reserved;
 } BFMatchVerifyOptions;
 
+/* The SIFT detector (bf_sift_*): SiftGPU as SiftGPU::SetParams configures it (first octave 0, four octaves, three DoG
+ * levels, no sub-pixel localisation, two orientations). zParameters*Default.txt values in brackets, taken when 0. */
+typedef struct BFSiftOptions {
+    uint32_t width, height;           /* s_widthSIFT x s_heightSIFT: the float intensity image; 32...4096 each */
+    uint32_t depthWidth, depthHeight; /* the filtered float depth image, at its own size; 1...4096 each */
+    uint32_t maxKeys;                 /* s_maxNumKeysPerImage [1024], <= BF_MATCH_MAX_KEYS_PER_IMAGE */
+    uint32_t featureCountThreshold;   /* GlobalUtil::_FeatureCountThreshold [150] */
+    float sensorDepthMin;             /* s_sensorDepthMin [0.1] m */
+    float sensorDepthMax;             /* s_sensorDepthMax [4.0] m */
+    float minKeyScale;                /* s_minKeyScale [3.0] */
+    float dogThreshold;               /* SiftParam::_dog_threshold [0.02 / 3] */
+    float edgeThreshold;              /* SiftParam::_edge_threshold [10] */
+    uint32_t reserved;
+} BFSiftOptions;
+
+#define BF_SIFT_LEVELS 12      /* 4 octaves x 3 DoG levels, index = octave * 3 + level */
+#define BF_SIFT_MAX_FILTER 33  /* KERNEL_MAX_WIDTH (ProgramCU.cu:54) */
+#define BF_SIFT_TRUNCATED 1u   /* bf_sift_result flag: more than maxKeys keys were found, the finest were dropped */
+
 #ifdef __cplusplus
 } /* extern "C" */
 
+static_assert(sizeof(BFSiftOptions) == 48, "BFSiftOptions is 48 B");
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
