@@ -1780,7 +1780,12 @@ int bf_preproc_create(uint32_t depthW, uint32_t depthH, uint32_t colorW, uint32_
     int prLeast = 0, prGreatest = 0;
     BF_HIP(hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest));
     BF_HIP(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prGreatest));
-    h->p = new Preproc(depthW, depthH, colorW, colorH, integrationW, integrationH, *opt, h->stream);
+    try {
+        h->p = new Preproc(depthW, depthH, colorW, colorH, integrationW, integrationH, *opt, h->stream);
+    } catch (...) {
+        (void)hipStreamDestroy(h->stream);
+        throw;
+    }
     *out = h.release();
     BF_CATCH
 }

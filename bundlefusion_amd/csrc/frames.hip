@@ -178,6 +178,12 @@ Preproc::Preproc(uint32_t dw, uint32_t dh, uint32_t cw, uint32_t ch, uint32_t iw
                  hipStream_t stream)
     : dw_(dw), dh_(dh), cw_(cw), ch_(ch), iw_(iw), ih_(ih), opt_(o), stream_(stream) {
     BF_REQUIRE(dw && dh && iw && ih, BF_ERR_ARG, "empty image size");
+    // k_resample scales by (in - 1) / (out - 1): equal sizes are copied, any other pair needs both >= 2
+    BF_REQUIRE((dw == iw && dh == ih) || (dw >= 2 && dh >= 2 && iw >= 2 && ih >= 2), BF_ERR_ARG,
+               "depth and integration sizes must be >= 2 when they differ");
+    // colour size 0 x 0: no colour image will be given (run() rejects one)
+    BF_REQUIRE((cw == 0 && ch == 0) || (cw == iw && ch == ih) || (cw && ch && iw >= 2 && ih >= 2), BF_ERR_ARG,
+               "colour size must be non-zero and the integration size >= 2 when they differ");
     BF_REQUIRE(o.erodeStructureSize >= 0 && o.erodeStructureSize <= MAXR, BF_ERR_ARG, "erode structure size 0..7");
     BF_REQUIRE(o.depthShift > 0.0f, BF_ERR_ARG, "depthShift");
     if (o.depthFilter) gauss_ = gauss_table(o.sigmaD);
@@ -189,6 +195,7 @@ Preproc::Preproc(uint32_t dw, uint32_t dh, uint32_t cw, uint32_t ch, uint32_t iw
 // CUDAImageManager::process: raw -> [erode x2 (raw <-> filtered)] -> [gauss | copy] -> resample
 void Preproc::run(const uint16_t* depthU16, const uint8_t* rgbx, float* depthOut, uint8_t* colorOut, int slot) {
     BF_REQUIRE(slot == 0 || slot == 1, BF_ERR_ARG, "preprocessing buffer slot 0 / 1");
+    BF_REQUIRE(!(rgbx && colorOut) || (cw_ && ch_), BF_ERR_ARG, "colour image given to a preprocessor created without a colour size");
     const uint32_t n = dw_ * dh_;
     slot_ = slot;
     float* raw = a_[slot].p;

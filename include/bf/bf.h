@@ -840,7 +840,9 @@ int bf_params_preprocess_options(const bf_params* p, float depthShift, BFPreproc
 
 /* CUDAImageManager::process (CUDAImageManager.cpp:22-158): ushort depth -> metres, erodeDepthMap x2,
  * gaussFilterDepthMap, nearest resampling of depth and colour to the integration size. All image
- * pointers are device pointers; work is queued on the handle's stream. */
+ * pointers are device pointers; work is queued on the handle's stream. Equal sizes are copied (legal at any
+ * size); where depth or colour is resampled, both of its sizes must be >= 2 in depth / integration and non-zero
+ * in colour, else BF_ERR_ARG. Colour size 0 x 0: no colour image (bf_preproc_run with one returns BF_ERR_ARG). */
 int bf_preproc_create(uint32_t depthW, uint32_t depthH, uint32_t colorW, uint32_t colorH, uint32_t integrationW,
                       uint32_t integrationH, const BFPreprocessOptions* opt, bf_preproc** out);
 int bf_preproc_destroy(bf_preproc* p);
