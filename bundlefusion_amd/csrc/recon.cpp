@@ -139,7 +139,6 @@ Recon::Recon(const BFHashParams& hp, const BFSceneOptions* so, const BFDepthCame
     global_.reset(new Solver(make_solver_config(opt_.maxKeyframes, opt_.maxGlobalCorr, &opt_.solver), baStream_));
     tm_.reset(new TrajectoryManager(opt_.maxFrames, opt_.topNActive, opt_.minPoseDistSqrt));
     if (opt_.enableTiming) {
-        scene_->integrateClock().enable(true);
         scene_->applyClock().enable(true);
         // one voxel-pass launch in four carries the timing events (every launch stamped cost the bench
         // ~0.9 % of its frame rate: 1 616 against 1 631 frames/s untimed); the mean is taken over those
@@ -1089,8 +1088,6 @@ BFReconStats Recon::stats() {
     synchronize();
     BFReconStats s = st_;
     if (opt_.enableTiming) {
-        s.integrateKernelMs = scene_->integrateClock().totalMs();
-        s.integrateLaunches = scene_->integrateClock().launches();
         s.reintegrateKernelMs = scene_->applyClock().totalMs();
         s.reintegrateLaunches = scene_->applyClock().launches();
         s.localSolveMs = local_->solveClock().totalMs();
@@ -1109,7 +1106,6 @@ void Recon::resetStats() {
     g_hostFrames = 0;
 #endif
     scene_->resetStats();
-    scene_->integrateClock().reset();
     scene_->applyClock().reset();
     local_->solveClock().reset();
     global_->solveClock().reset();

@@ -9,10 +9,11 @@
 //                                 only the allocated pool prefix instead of the whole hash table
 //   visible   int4[B]             compacted frustum list {x, y, z, ptr} (16 B vs 32 B HashEntry);
 //                                 GC walks this list, as the reference walks d_hashCompactified
-//   band      int4[24 B]          (op batches: one bin of B entries per op count) the subset of `visible` whose voxels can reach the truncation band
-//                                 of the current depth map (conservative cull against per-8x8-tile
-//                                 depth bounds) — the list integrate walks
-//   tiles     float2[tiles]       per-8x8-pixel-tile min/max of the valid depths of the current op(s)
+//   band      int4[24 B]          the work list of an op batch, one bin of B entries per op count: the allocated
+//                                 blocks whose voxels can reach the truncation band of some op's depth map
+//                                 (conservative cull against per-8x8-tile depth bounds) — the list the voxel
+//                                 pass walks
+//   tiles     float2[tiles]       per-8x8-pixel-tile min/max of the valid depths, per op of the batch
 //   tiles2    float2[tiles2]      the same per 32x32 pixels (footprints wider than 2x2 tiles)
 //   ctrl      uint32[16]          device-resident counters (heap counter, visible count, ...)
 //   cand/candSet/candSlot/ovf     alloc scratch (per-op candidate list, global dedup set)
@@ -31,10 +32,10 @@ enum Ctrl {
     C_CAND = 2,        // alloc candidates emitted
     C_OVF = 3,         // candidates whose bucket was full (collision-list path)
     C_HIGHWATER = 4,   // 1 + highest heap block index ever handed out
-    C_CANDPEAK = 5,    // largest alloc candidate count of one integrate / batch since the reset (may exceed the capacity)
+    C_CANDPEAK = 5,    // largest alloc candidate count of one op batch since the reset (may exceed the capacity)
     C_GC_LIST = 6,     // GC victims that touch a collision list (serial path)
     C_ERR = 7,         // error bits (1: candidate buffer overflow, 2: heap exhausted, 4: dedup set full)
-    C_BAND = 8,        // blocks of the visible list that may hold a voxel inside the truncation band
+    C_BAND = 8,        // no longer counted (the batch work list's counts are the C_OPBIN slots); zeroed per op
     C_TICKET = 9,      // last-workgroup ticket of k_alloc_insert (self-resetting)
     C_TICKET_GC = 10,  // last-workgroup ticket of k_gc (self-resetting)
     C_OPBIN = 16,      // op batches: work-list entries per op count (1..kMaxOps -> slots 16..39)
@@ -43,7 +44,7 @@ enum Ctrl {
 
 struct SceneConfig {
     BFHashParams hp;
-    uint32_t candCapacity;   // max alloc candidates per integrate
+    uint32_t candCapacity;   // max alloc candidates per op batch
     uint32_t shardCount;     // >1: spatial ownership sharding across GPUs
     uint32_t shardIndex;
     float shardChunk;        // ownership chunk edge in metres (default 1 m, the streaming chunk)
@@ -84,8 +85,8 @@ public:
     ~Scene();
 
     void reset();
-    // integrate (deint=false) / de-integrate (deint=true) one frame; depth/color are device
-    // pointers (float / uchar4 per pixel, W*H of cam). T is camera->world.
+    // integrate (deint=false) / de-integrate (deint=true) one frame, as a one-op applyOps batch;
+    // depth/color are device pointers (float / uchar4 per pixel, W*H of cam). T is camera->world.
     void integrate(const BFMat4& T, const float* depth, const uint8_t* color, const BFDepthCameraParams& cam,
                    bool deint, const uint32_t* bitMask);
     // re-integration of one frame: de-integrate with Told then integrate with Tnew as a two-op
@@ -97,7 +98,8 @@ public:
     // a kernel that applies the ops to each voxel in sequence order (one read, one write). Voxel
     // values equal the sequential calls; `visible` is the frustum list of the last op, as the
     // reference's garbageCollect after the loop sees it.
-    void applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& cam);
+    // bitMask (optional): the reference's streaming mask; blocks of streamed-out chunks are not allocated.
+    void applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& cam, const uint32_t* bitMask = nullptr);
     static size_t tileCount(const BFDepthCameraParams& cam);  // float2 per depth map of a VoxelOp tile cache
     static size_t dcCount(const BFDepthCameraParams& cam);    // uint2 per depth map of a VoxelOp dc image
     KernelClock& applyClock() { return applyClock_; }  // k_apply_ops launches
@@ -131,7 +133,6 @@ public:
     const uint32_t* dCtrl() const { return ctrl_.p; }
     uint32_t* dCtrlMut() { return ctrl_.p; }
     size_t deviceBytes() const;
-    KernelClock& integrateClock() { return integrateClock_; }  // k_integrate launches (bench roofline)
 
     // CUDARayCastSDF::render (CUDARayCastSDF.cpp:38-72) after setLastRigidTransformAndCompactify:
     // frustum compactify for camera T (cam = depth-camera frustum params), ray-interval splat
@@ -150,7 +151,6 @@ public:
     uint32_t extractMesh(const BFMarchingCubesParams& p, BFMcTriangle* out, uint32_t cap, uint32_t* total);
 
 private:
-    void alloc(const float* depth, const BFDepthCameraParams& cam, const uint32_t* bitMask);
     void beginOp();
 
     SceneConfig cfg_;
@@ -183,8 +183,6 @@ private:
     uint32_t* errMirror_ = nullptr;  // pinned host word written by k_gc (enableErrorMirror)
     uint32_t candSetMask_;
     int numCUs_;
-    unsigned integrateGrid_[2] = {0, 0};
-    KernelClock integrateClock_;
     KernelClock renderClock_, splatClock_;
     DevBuf<unsigned long long> renderStats_;
     DevBuf<uint4> blockMask_;  // per work-list entry of an op batch: which ops may update each z-half (uint2) / quarter

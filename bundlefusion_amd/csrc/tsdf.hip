@@ -9,10 +9,11 @@
 //    stable try-lock loop and its host round trips (CUDASceneRepHashSDF.h:335-348).
 //  * compactify streams the allocated prefix of a 16-B per-block position array instead of
 //    the whole 32-B-per-entry hash table, with wave ballot + popcount compaction.
-//  * integrate runs one wave per 8^3 block (8 z-slices of 64 voxels), touching a voxel's
-//    12 B only when it lies inside the truncation band.
+//  * every integrate / de-integrate is an op batch (Scene::applyOps; one frame = a one-op batch):
+//    the voxel pass runs one wave per 8^3 block (8 z-slices of 64 voxels), touching a voxel's
+//    12 B only when it lies inside the truncation band of some op.
 //  * GC reads a per-block count of voxels with (uint)weight != 0, maintained by the
-//    integrate kernel, instead of re-reading 512 voxels per block.
+//    voxel pass, instead of re-reading 512 voxels per block.
 #include "tsdf.h"
 #include "../../include/bf/bf.h"
 #include "hash_dev.h"
@@ -43,10 +44,7 @@ struct HashArgs {
     uint32_t* blockCount;
     int4* visible;
     int4* band;
-    const float2* tiles;
-    uint32_t tilesW, tilesH;
-    const float2* tiles2;  // 32x32-pixel depth bounds (footprints wider than 2x2 fine tiles)
-    uint32_t tiles2W;
+    uint32_t tilesW, tiles2W;  // row lengths of the ops' fine / coarse depth-bound tile arrays (OpTable)
     uint32_t* ctrl;
     unsigned long long* stats;  // [STAT_SLOTS][16] counters, field order of BFTsdfStats
     uint32_t numBuckets, numEntries, numBlocks, maxList;
@@ -279,22 +277,6 @@ __device__ __forceinline__ void depth_tile_wave(uint32_t t, const float* __restr
     }
 }
 
-// Per-op counter reset fused with the depth-bound tiles of the op.
-__global__ __launch_bounds__(256) void k_begin_op_tiles(uint32_t* ctrl, unsigned long long* stats,
-                                                        const float* __restrict__ depthImg, uint32_t W, uint32_t H,
-                                                        uint32_t tilesW, uint32_t tilesH, uint32_t tiles2W, uint32_t tiles2H,
-                                                        float maxDist, float2* tiles, float2* tiles2, uint32_t nops) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctrl[C_VISIBLE] = 0;
-        ctrl[C_BAND] = 0;
-        ctrl[C_CAND] = 0;
-        ctrl[C_OVF] = 0;
-        stats[S_OPS] += nops;
-    }
-    depth_tile_wave((blockIdx.x * blockDim.x + threadIdx.x) >> 6, depthImg, W, H, tilesW, tilesH, tiles2W, tiles2H, maxDist,
-                    tiles, tiles2);
-}
-
 // The screen rectangle of a block's corner projections, grown for the voxel pass's pixel rule: a voxel at
 // screen x takes column (int)(x + 0.5), truncated toward zero, so x in (-1.5, -0.5] lands in column 0. The
 // rectangle [floor(lo - 0.5), floor(hi + RECT_HI)] holds every column a voxel can take; at the left / top edge
@@ -302,72 +284,18 @@ __global__ __launch_bounds__(256) void k_begin_op_tiles(uint32_t* ctrl, unsigned
 // corner projections' rounding (~1e-4 px): without it a corner computed 7.5e-5 px past -1.5 dropped a half
 // whose corner voxel lands in row 0 (test_app_gpu's end phase, one weight off).
 constexpr float RECT_HI = 1.5f + 0x1p-6f;
-// Conservative test that a block may contain a voxel integrate will update: project the 8 voxel-
-// centre corners (convex hull -> bounding pixel rectangle, grown by one pixel), take the depth
-// bounds of the covered tiles and reject when every depth is too far behind or in front of the
-// block for |d - z| < truncation + truncScale * d to hold (1 mm slack for rounding, ~1000x the
-// float error). Exactness: a rejected block has no voxel with an in-band sample, so skipping it
-// changes no voxel. The corner projections use rcp (1 ulp, far inside the one-pixel growth);
-// footprints within 3x3 fine (8-pixel) tiles read those tiles, wider ones up to 3x3 coarse
-// (16-pixel) tiles, all loads independent.
-// z0 / z1: the voxel z-range (offsets in the block) the test covers; a half-block test covers 0..3
-// or 4..7, the block test 0..7
-__device__ bool block_may_update(const HashArgs& A, const BFDepthCameraParams& cam, const BFMat4& Tinv, int bx, int by,
-                                 int bz, const float2* __restrict__ tiles, const float2* __restrict__ tiles2, int z0 = 0,
-                                 int z1 = BF_SDF_BLOCK_SIZE - 1) {
-    const f3 c0 = block_to_world(bx, by, bz, A.voxelSize) + mk3(0.0f, 0.0f, A.voxelSize * (float)z0);
-    const float ext = A.voxelSize * (float)(BF_SDF_BLOCK_SIZE - 1), extz = A.voxelSize * (float)(z1 - z0);
-    float zlo = INFINITY, zhi = -INFINITY, xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const f3 w = c0 + mk3((k & 1) ? ext : 0.0f, (k & 2) ? ext : 0.0f, (k & 4) ? extz : 0.0f);
-        const f3 p = xform(Tinv, w);
-        if (!(p.z > 1e-3f)) return true;  // straddles the camera plane: keep
-        const float rz = __builtin_amdgcn_rcpf(p.z);
-        const float sx = p.x * cam.fx * rz + cam.mx, sy = p.y * cam.fy * rz + cam.my;
-        zlo = fminf(zlo, p.z); zhi = fmaxf(zhi, p.z);
-        xlo = fminf(xlo, sx); xhi = fmaxf(xhi, sx);
-        ylo = fminf(ylo, sy); yhi = fmaxf(yhi, sy);
-    }
-    const float W = (float)cam.imageWidth, H = (float)cam.imageHeight;
-    const float fx0 = floorf(xlo - 0.5f), fx1 = floorf(xhi + RECT_HI), fy0 = floorf(ylo - 0.5f), fy1 = floorf(yhi + RECT_HI);
-    if (fx1 < 0.0f || fy1 < 0.0f || fx0 > W - 1.0f || fy0 > H - 1.0f) return false;  // every voxel off-screen
-    const int x0 = (int)fmaxf(fx0, 0.0f), x1 = (int)fminf(fx1, W - 1.0f);
-    const int y0 = (int)fmaxf(fy0, 0.0f), y1 = (int)fminf(fy1, H - 1.0f);
-    const int tx0 = x0 / DEPTH_TILE, tx1 = x1 / DEPTH_TILE, ty0 = y0 / DEPTH_TILE, ty1 = y1 / DEPTH_TILE;
-    float dlo = INFINITY, dhi = -INFINITY;
-    if (tx1 - tx0 <= 2 && ty1 - ty0 <= 2) {  // footprint within 3x3 fine tiles (<= 17 px)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const float2 t = tiles[min(ty0 + j, ty1) * A.tilesW + min(tx0 + i, tx1)];
-                dlo = fminf(dlo, t.x);
-                dhi = fmaxf(dhi, t.y);
-            }
-    } else {
-        const int cx0 = x0 / DEPTH_TILE2, cx1 = x1 / DEPTH_TILE2, cy0 = y0 / DEPTH_TILE2, cy1 = y1 / DEPTH_TILE2;
-        if (cx1 - cx0 > 2 || cy1 - cy0 > 2) return true;  // very close block: keep
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const float2 t = tiles2[min(cy0 + j, cy1) * A.tiles2W + min(cx0 + i, cx1)];
-                dlo = fminf(dlo, t.x);
-                dhi = fmaxf(dhi, t.y);
-            }
-    }
-    if (!(dlo <= dhi)) return false;  // no integrable depth under the block
-    const float slack = 0.001f;  // >> the float error of zlo / zhi and of the kernel's band test
-    if (dlo * (1.0f - A.truncScale) >= zhi + A.truncation + slack) return false;  // surface far behind
-    if (dhi * (1.0f + A.truncScale) <= zlo - A.truncation - slack) return false;  // surface far in front
-    return true;
-}
-
-// block_may_update for the two z-halves of the block at once (bit h: half h, voxel z 4h..4h+3, may
-// hold an in-band voxel), from per-op constants (cull_op_consts, 28 floats). The screen footprint and
-// its depth bounds are the whole block's (a superset of each half's pixels: still conservative); the
-// depth range is each half's own. The camera-space corner positions are affine in the corner
+// The band cull: a conservative test that a z-half of a block may contain a voxel an op will update,
+// for both halves at once (bit h: half h, voxel z 4h..4h+3), from per-op constants (cull_op_consts, 28
+// floats). It projects the 8 voxel-centre corners (convex hull -> bounding pixel rectangle, grown by
+// one pixel), takes the depth bounds of the covered tiles and rejects a half when every depth is too
+// far behind or in front of it for |d - z| < truncation + truncScale * d to hold (1 mm slack for
+// rounding, ~1000x the float error). Exactness: a rejected half has no voxel with an in-band sample,
+// so skipping it changes no voxel. The corner projections use rcp (1 ulp, far inside the one-pixel
+// growth); footprints within 3x3 fine (8-pixel) tiles read those tiles, wider ones up to 3x3 coarse
+// (16-pixel) tiles, all loads independent; a block that reaches the camera plane or is wider still is
+// kept. The screen footprint and its depth bounds are the whole block's (a superset of each half's
+// pixels: still conservative); the depth range is each half's own.
+// The camera-space corner positions are affine in the corner
 // offsets, so the block's corner voxel is transformed once (fma, the focal lengths folded into the
 // x / y rows) and the other corners are that point plus sums of the three scaled columns; each
 // half's depth range is the corner point's depth plus per-op minima / maxima of the column terms.
@@ -730,11 +658,6 @@ __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __
     // serialised ~10^5 atomics per frame on them)
     if (__syncthreads_or(emitted != 0 ? 1 : 0)) flush_stats2(A.stats, S_CAND, emitted, -1, 0);
 }
-__global__ __launch_bounds__(256) void k_alloc_collect(HashArgs A, const float* __restrict__ depthImg,
-                                                       BFDepthCameraParams cam, BFMat4 T, BFMat4 Tinv,
-                                                       unsigned long long* __restrict__ cand, uint32_t candCap) {
-    alloc_collect(A, depthImg, cam, T, Tinv, cand, candCap);
-}
 // batched: blockIdx.z selects the integrate op of the table (all ops' candidates land in one list;
 // the global dedup of k_alloc_insert removes blocks several ops want)
 // waves per SIMD asked of the compiler for the batched walk: 8 (63 VGPRs, 78 SGPRs with 65 spilled to VGPR lanes)
@@ -917,122 +840,50 @@ __device__ void alloc_overflow_serial(const HashArgs& A, const unsigned long lon
 }
 
 // compactifyHashAllInOneKernel, CUDASceneRepHashSDF.cu:324-366: stream the allocated pool
-// prefix [0, highWater), keep the in-frustum blocks; wave ballot + one atomic per wave.
-enum CompactMode { CM_FRUSTUM = 0, CM_INTEGRATE = 1 };
-
-// MODE selects the lists a pass builds:
-//   CM_FRUSTUM    visible (the API's compactify / the raycaster)
-//   CM_INTEGRATE  visible (GC list) + band (integrate's work list); releases the alloc dedup set
-template <int MODE>
-__global__ __launch_bounds__(256) void k_compactify(HashArgs A, BFDepthCameraParams cam, BFMat4 Tinv, uint32_t candCap,
-                                                    const int* __restrict__ candSlot, unsigned long long* candSet) {
-    if (MODE == CM_INTEGRATE) {  // release this op's alloc dedup-set slots
-        const uint32_t n = min(A.ctrl[C_CAND], candCap);
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-            const int sl = candSlot[i];
-            if (sl >= 0) candSet[sl] = EMPTY_KEY;
-        }
-    }
+// prefix [0, highWater), keep the in-frustum blocks in `visible` (the API's compactify / the
+// raycaster); wave ballot + one atomic per workgroup iteration.
+__global__ __launch_bounds__(256) void k_compactify(HashArgs A, BFDepthCameraParams cam, BFMat4 Tinv) {
     // one list append per workgroup iteration: wave ballots -> LDS prefix over the 4 waves ->
-    // a single atomic per list (instead of one per wave on the hot counter)
-    __shared__ uint32_t s_cnt[2][4], s_base[2];
+    // a single atomic (instead of one per wave on the hot counter)
+    __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t hw = A.ctrl[C_HIGHWATER];
     const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-    unsigned long long scanned = 0, vis = 0, band = 0;
+    unsigned long long scanned = 0, vis = 0;
     for (uint32_t base = blockIdx.x * blockDim.x; base < hw; base += gridDim.x * blockDim.x) {
         const uint32_t i = base + threadIdx.x;
         int4 bp = make_int4(0, 0, 0, 0);
         if (i < hw) bp = A.blockPos[i];
         const bool alloc = bp.w != 0;
         const bool inFr = alloc && block_in_frustum_fast(cam, Tinv, bp.x, bp.y, bp.z, A.voxelSize);
-        const bool inb = MODE != CM_FRUSTUM && inFr && block_may_update(A, cam, Tinv, bp.x, bp.y, bp.z, A.tiles, A.tiles2);
-        const bool keepVis = inFr;
-        const unsigned long long m0 = __ballot(keepVis), m1 = __ballot(inb);
-        if (lane == 0) {
-            s_cnt[0][wv] = (uint32_t)__popcll(m0);
-            s_cnt[1][wv] = (uint32_t)__popcll(m1);
+        const unsigned long long m0 = __ballot(inFr);
+        if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(m0);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_base = tot ? atomicAdd(&A.ctrl[C_VISIBLE], tot) : 0u;
         }
         __syncthreads();
-        if (threadIdx.x < 2) {
-            const uint32_t tot = s_cnt[threadIdx.x][0] + s_cnt[threadIdx.x][1] + s_cnt[threadIdx.x][2] + s_cnt[threadIdx.x][3];
-            s_base[threadIdx.x] = tot ? atomicAdd(&A.ctrl[threadIdx.x == 0 ? C_VISIBLE : C_BAND], tot) : 0u;
-        }
-        __syncthreads();
-        uint32_t off0 = s_base[0], off1 = s_base[1];
-        for (uint32_t k = 0; k < wv; k++) {
-            off0 += s_cnt[0][k];
-            off1 += s_cnt[1][k];
-        }
-        const int4 ent = make_int4(bp.x, bp.y, bp.z, (int)i);
-        if (keepVis) A.visible[off0 + __popcll(m0 & lanemask_lt())] = ent;
-        if (inb) A.band[off1 + __popcll(m1 & lanemask_lt())] = ent;
+        uint32_t off0 = s_base;
+        for (uint32_t k = 0; k < wv; k++) off0 += s_cnt[k];
+        if (inFr) A.visible[off0 + __popcll(m0 & lanemask_lt())] = make_int4(bp.x, bp.y, bp.z, (int)i);
         scanned += alloc ? 1 : 0;
         vis += inFr ? 1 : 0;
-        band += inb ? 1 : 0;
         __syncthreads();  // s_cnt / s_base reuse
     }
     flush_stats2(A.stats, S_SCANNED, scanned, S_VISIBLE, vis);
-    if (MODE != CM_FRUSTUM) {
-        __syncthreads();  // thread 0 of the first flush reads its LDS sums before they are reset
-        flush_stats2(A.stats, S_BAND, band, -1, 0);
-    }
-}
-
-// ---- divisions whose result only feeds an integer ------------------------------------------------
-// f2i(num / den + m + 0.5f) and roundf(num / den) with the quotient of the reference's IEEE division.
-// The quotient is first formed as num * rcp(den) (v_rcp_f32, 1 ulp): |q_approx - q| <= 2^-22 |q|.
-// The integer outcome is a step function of the quotient, monotone through the remaining rounded
-// additions, so it can only differ when a step (an integer for f2i, a half-integer for roundf) lies
-// within that bound plus the rounding of the later additions. Such lanes (~1e-4 of them), and
-// non-finite quotients, redo the IEEE division: the result is bit-identical to the plain code.
-// The exact division runs only in waves where some lane needs it: the branch is taken on the wave's
-// ballot and holds an empty asm statement, so the compiler cannot if-convert (speculate) it.
-__device__ __forceinline__ int proj_coord(float num, float den, float m) {
-    const float qa = num * __builtin_amdgcn_rcpf(den);
-    float t = (qa + m) + 0.5f;
-    const float eps = (fabsf(qa) + 2.0f * fabsf(t) + 2.0f) * 0x1p-21f;
-    const bool need = !(fabsf(t - rintf(t)) > eps);
-    if (__builtin_amdgcn_ballot_w64(need)) {
-        asm volatile("" ::: "memory");
-        const float te = (num / den + m) + 0.5f;
-        t = need ? te : t;
-    }
-    return f2i(t);
-}
-__device__ __forceinline__ float round_quot(float num, float den, float rden) {
-    float q = num * rden;
-    const float aq = fabsf(q);
-    const float eps = (aq + 1.0f) * 0x1p-21f;
-    const bool need = !(fabsf((aq - floorf(aq)) - 0.5f) > eps);
-    if (__builtin_amdgcn_ballot_w64(need)) {
-        asm volatile("" ::: "memory");
-        const float e = num / den;
-        q = need ? e : q;
-    }
-    return roundf(q);
 }
 
 // Integrate colour blend of integrateDepthMapKernel (CUDASceneRepHashSDF.cu:486-496): per channel
 // u8(clamp(roundf(0.2f * cu + 0.8f * oc), 0, 254.5)), or the new colour when the voxel is empty. The
-// float expression lies within 1e-5 of (cu + 4 oc) / 5, whose fractional part is a multiple of 0.2,
-// so its roundf is the integer (2 cu + 8 oc + 5) / 10 = ((2 cu + 8 oc + 5) * 6554) >> 16 (exact for
-// all 65536 (cu, oc): checked exhaustively in tests/test_oracle_tsdf.py). Integer ops replace the
-// float blend + roundf + clamp.
-__device__ __forceinline__ uint32_t blend_channel(uint32_t cu, uint32_t oc, bool empty) {
-    const uint32_t m = ((2u * cu + 8u * oc + 5u) * 6554u) >> 16;
-    return min(empty ? cu : m, 254u);
-}
-__device__ __forceinline__ uint32_t blend_color(uint32_t c, uint32_t col, bool empty) {
-    return blend_channel(c & 0xFF, col & 0xFF, empty) | (blend_channel((c >> 8) & 0xFF, (col >> 8) & 0xFF, empty) << 8) |
-           (blend_channel((c >> 16) & 0xFF, (col >> 16) & 0xFF, empty) << 16) | (255u << 24);
-}
-// blend_color with packed FP32 arithmetic (the batch pass: 4 VALU fewer per integrate update than the
-// integer form, k_apply_ops 619 / 618 -> 593 / 596 us, A/B pairs in
+// float expression lies within 1e-5 of (cu + 4 oc) / 5, whose fractional part is a multiple of 0.2.
+// Here with packed FP32 arithmetic (4 VALU fewer per integrate update than an integer
+// form, k_apply_ops 619 / 618 -> 593 / 596 us, A/B pairs in
 // profiles/r5_apply_experiments.txt): (cu + 4 oc) / 5 as (4 oc + cu)
 // x 0.2f (operands exact integers, product within 1e-5 of the quotient, whose fraction is a multiple of
 // 0.2), rounded by rintf (never a tie), min 254, and packed by v_cvt_pk_u8_f32 (an exact conversion of
-// an integral value). An empty voxel takes oc = cu, for which the quotient is cu. Same bytes as
-// blend_color for every (cu, oc, empty).
+// an integral value). An empty voxel takes oc = cu, for which the quotient is cu (min(cu, 254) comes
+// out). Same bytes as the clamped float expression for all 65536 (cu, oc): checked exhaustively in
+// tests/test_oracle_tsdf.py.
 __device__ __forceinline__ uint32_t blend_color_f(uint32_t c, uint32_t col, bool empty) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const uint32_t o = empty ? c : col;
@@ -1096,15 +947,25 @@ __device__ __forceinline__ void voxel_deint_color(float w0, uint32_t col, uint32
     }
 }
 
-// Two voxels of one lane column, (x, y, z) and (x, y, z + 1), projected together: every float
-// operation is the scalar path's (xform's ((e0 x + e1 y) + e2 z) + e3, then fx * x, the rcp quotient,
+// ---- the voxel's pixel: a division whose result only feeds an integer ---------------------------
+// f2i(num / den + m + 0.5f) with the quotient of the reference's IEEE division. The quotient is first
+// formed as qa = num * rcp(den) (v_rcp_f32, 1 ulp): |qa - q| <= 2^-22 |q|. The integer outcome is a
+// step function of the quotient, monotone through the remaining rounded additions, so it can only
+// differ when an integer lies within that bound plus the rounding of the later additions of
+// t = (qa + m) + 0.5, i.e. within (|qa| + 2 |t| + 2) 2^-21 of t. Such lanes (~1e-4 of them), and
+// non-finite quotients, redo the IEEE division: the result is bit-identical to the plain code. The
+// exact division runs only in waves where some lane needs it: the branch is taken on the wave's
+// ballot and holds an empty asm statement, so the compiler cannot if-convert (speculate) it.
+//
+// Two voxels of one lane column, (x, y, z) and (x, y, z + 1), are projected together: every float
+// operation is the scalar form's (xform's ((e0 x + e1 y) + e2 z) + e3, then fx * x, the rcp quotient,
 // + m, + 0.5), done elementwise on 2-wide vectors so that it issues as packed-FP32 instructions
 // (v_pk_mul_f32 / v_pk_add_f32: two IEEE results per instruction, no contraction). The exactness
-// check and the IEEE fallback of proj_coord follow per element.
+// check and the IEEE fallback follow per element.
 typedef float f2v __attribute__((ext_vector_type(2)));
-// Exactness test of a rounded screen coordinate t = (num * rcp(den) + m) + 0.5 against a bound that
-// is constant per launch: eps_c = (3 (max(W, H) + 2) + max(|mx|, |my|) + 3) 2^-21 is at least
-// proj_coord's per-lane bound (|qa| + 2 |t| + 2) 2^-21 for every lane with |t| <= max(W, H) + 2.
+// The exactness test against a bound that is constant per launch:
+// eps_c = (3 (max(W, H) + 2) + max(|mx|, |my|) + 3) 2^-21 is at least
+// the per-lane bound (|qa| + 2 |t| + 2) 2^-21 for every lane with |t| <= max(W, H) + 2.
 // Lanes beyond that are off-screen for the fast and the exact quotient alike (their distance to the
 // screen exceeds the quotient error), so the pixel decision is the IEEE one everywhere.
 __device__ __forceinline__ bool proj_needs_exact(float t, float epsc) { return !(fabsf(t - rintf(t)) > epsc); }
@@ -1138,112 +999,6 @@ __device__ __forceinline__ void voxel_pixel2b(const BFDepthCameraParams& cam, co
     pz = p[2];
     off0 = ((ux0 < wc) & (uy0 < cam.imageHeight)) ? __umul24(uy0, W8) + (ux0 << 3) : 0xFFFFFFFFu;
     off1 = ((ux1 < wc) & (uy1 < cam.imageHeight)) ? __umul24(uy1, W8) + (ux1 << 3) : 0xFFFFFFFFu;
-}
-
-// integrateDepthMapKernel<deIntegrate>, CUDASceneRepHashSDF.cu:420-521. One wave per block:
-// lane = (y, x) of a z-slice, 8 slices. Voxel bytes are touched only inside the band.
-template <bool DEINT, int ZC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_integrate(HashArgs A, const float* __restrict__ depthImg,
-                                                   const uint32_t* __restrict__ colorImg, BFDepthCameraParams cam,
-                                                   BFMat4 Tinv) {
-    const uint32_t nvis = A.ctrl[C_BAND];
-    const uint32_t lane = lane_id();
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int lx = lane & 7, ly = lane >> 3;
-    const uint32_t W = cam.imageWidth, H = cam.imageHeight;
-    const float wUpd = 1.0f;  // weightUpdate forced to 1 (:465-466)
-    unsigned long long updated = 0;
-    for (uint32_t b = wave; b < nvis; b += nwaves) {
-        const int4 e = A.band[b];
-        const int bx = e.x * BF_SDF_BLOCK_SIZE + lx, by = e.y * BF_SDF_BLOCK_SIZE + ly, bz = e.z * BF_SDF_BLOCK_SIZE;
-        int dcount = 0;
-        uint32_t nupd = 0;
-        // ZC z-slices per round (8: one round, most ILP; 4: two rounds, fewer VGPRs, more waves)
-#pragma unroll
-        for (int z0 = 0; z0 < BF_SDF_BLOCK_SIZE; z0 += ZC) {
-        // phase 1: project the lane's voxels and issue the depth gathers back to back
-        float depth[ZC], pz[ZC];
-        uint32_t pix[ZC];
-#pragma unroll
-        for (int zi = 0; zi < ZC; zi++) {
-            const int z = z0 + zi;
-            const f3 pf = xform(Tinv, vvox_to_world(bx, by, bz + z, A.voxelSize));
-            const uint32_t ux = (uint32_t)proj_coord(pf.x * cam.fx, pf.z, cam.mx);
-            const uint32_t uy = (uint32_t)proj_coord(pf.y * cam.fy, pf.z, cam.my);
-            const bool on = ux < W && uy < H && colorImg != nullptr;  // colour NULL: no update (:441-448)
-            pix[zi] = on ? uy * W + ux : 0xFFFFFFFFu;
-            pz[zi] = pf.z;
-            depth[zi] = on ? depthImg[pix[zi]] : -INFINITY;
-        }
-        // phase 2: band test, then issue the in-band voxel and colour loads together
-        float sdfv[ZC], osdf[ZC], ow[ZC];
-        uint32_t oc[ZC], cc[ZC];
-        uint32_t band = 0;
-#pragma unroll
-        for (int zi = 0; zi < ZC; zi++) {
-            const int z = z0 + zi;
-            const float dz = depth[zi];
-            float sdf = dz - pz[zi];
-            const float tr = A.truncation + A.truncScale * dz;
-            const bool in = dz != -INFINITY && dz < A.maxIntegrationDistance && fabsf(sdf) < tr;
-            sdf = (sdf >= 0.0f) ? fminf(tr, sdf) : fmaxf(-tr, sdf);
-            sdfv[zi] = sdf;
-            osdf[zi] = 0.0f; ow[zi] = 0.0f; oc[zi] = 0u; cc[zi] = 0u;
-            if (in) {
-                band |= 1u << zi;
-                // one 12-B load per voxel (global_load_dwordx3) instead of three dword loads
-                const Vox3 v = *reinterpret_cast<const Vox3*>(A.voxels + (size_t)e.w * BF_VOXELS_PER_BLOCK + (uint32_t)(z * 64 + lane));
-                osdf[zi] = __uint_as_float(v.a);
-                ow[zi] = __uint_as_float(v.b);
-                oc[zi] = v.c;
-                cc[zi] = colorImg[pix[zi]];
-            }
-        }
-        // phase 3: running average (integrate) or its inverse (de-integrate), store
-#pragma unroll
-        for (int zi = 0; zi < ZC; zi++) {
-            const int z = z0 + zi;
-            if (!(band & (1u << zi))) continue;
-            const uint32_t c = cc[zi];
-            const float cu0 = (float)(c & 0xFF), cu1 = (float)((c >> 8) & 0xFF), cu2 = (float)((c >> 16) & 0xFF);
-            const uint32_t o = oc[zi];
-            const float oc0 = (float)(o & 0xFF), oc1 = (float)((o >> 8) & 0xFF), oc2 = (float)((o >> 16) & 0xFF);
-            const float w0 = ow[zi], s0 = osdf[zi], sdf = sdfv[zi];
-            float r0, r1, r2, nsdf, nw;
-            uint32_t ncol;
-            if (!DEINT) {
-                ncol = blend_color(c, o, w0 == 0.0f);
-                nsdf = (sdf * wUpd + s0 * w0) / (wUpd + w0);
-                nw = fminf(A.weightMax, wUpd + w0);
-            } else {
-                const float den = w0 - wUpd, rden = __builtin_amdgcn_rcpf(den);
-                r0 = fmaxf(0.0f, fminf(round_quot(oc0 * w0 - cu0 * wUpd, den, rden), 254.5f));
-                r1 = fmaxf(0.0f, fminf(round_quot(oc1 * w0 - cu1 * wUpd, den, rden), 254.5f));
-                r2 = fmaxf(0.0f, fminf(round_quot(oc2 * w0 - cu2 * wUpd, den, rden), 254.5f));
-                ncol = (uint32_t)(uint8_t)r0 | ((uint32_t)(uint8_t)r1 << 8) | ((uint32_t)(uint8_t)r2 << 16) | (255u << 24);
-                nsdf = (s0 * w0 - sdf * wUpd) / (w0 - wUpd);
-                nw = fmaxf(0.0f, w0 - wUpd);
-                if (nw <= 0.001f) { nsdf = 0.0f; ncol = 0u; nw = 0.0f; }
-            }
-            Vox3 nv;
-            nv.a = __float_as_uint(nsdf);
-            nv.b = __float_as_uint(nw);
-            nv.c = ncol;
-            *reinterpret_cast<Vox3*>(A.voxels + (size_t)e.w * BF_VOXELS_PER_BLOCK + (uint32_t)(z * 64 + lane)) = nv;  // dwordx3 store
-            // per-block count of voxels with (uint)weight != 0 (GC decision, :606/:625)
-            dcount += (int)(nw >= 1.0f) - (int)(w0 >= 1.0f);
-            nupd++;
-        }
-        }  // z0
-        const unsigned long long anyChange = __ballot(dcount != 0);
-        if (anyChange) {
-            for (int off = 32; off > 0; off >>= 1) dcount += __shfl_xor(dcount, off);
-            if (lane == 0 && dcount != 0) atomicAdd(&A.blockCount[(uint32_t)e.w], (uint32_t)dcount);
-        }
-        updated += nupd;
-    }
-    flush_stats2(A.stats, S_VOXELS, updated, S_RMW, updated);
 }
 
 // ---- op batches (Scene::applyOps) ---------------------------------------------------------------
@@ -1827,7 +1582,7 @@ static HashArgs make_args(const SceneConfig& cfg, BFHashEntry* hash, uint32_t* h
                           int4* vis, uint32_t* ctrl, unsigned long long* st, const uint32_t* bitMask) {
     HashArgs a;
     a.hash = hash; a.heap = heap; a.voxels = vox; a.blockPos = bp; a.blockCount = bc; a.visible = vis; a.ctrl = ctrl; a.stats = st;
-    a.band = nullptr; a.tiles = nullptr; a.tilesW = a.tilesH = 0; a.tiles2 = nullptr; a.tiles2W = 0;
+    a.band = nullptr; a.tilesW = a.tiles2W = 0;
     a.numBuckets = cfg.hp.hashNumBuckets;
     a.numEntries = cfg.hp.hashNumBuckets * BF_HASH_BUCKET_SIZE;
     a.numBlocks = cfg.hp.numSDFBlocks;
@@ -1909,11 +1664,7 @@ Scene::Scene(const SceneConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(st
     numCUs_ = prop.multiProcessorCount;
     renderStats_.alloc((size_t)kRenderStatSlots * kRenderStatFields);  // RenderStat counters (raycast.hip)
     BF_HIP(hipMemsetAsync(renderStats_.p, 0, renderStats_.bytes(), stream_));
-    // k_integrate walks its block list with a static grid stride: size the grid to exactly the
-    // resident workgroups, so every wave gets the same share in one round (no tail round)
-    int occ0 = 0, occ1 = 0, occA = 0;
-    BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ0, k_integrate<false, 4>, 256, 0));
-    BF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, k_integrate<true, 4>, 256, 0));
+    int occA = 0;
     // One-wave workgroups: a wave's slot is handed on when that wave ends instead of when the slowest of its
     // workgroup's four ends (the waves of a workgroup draw blocks of different cost, and the workgroup's end-of-
     // pass counter flush waited for all four): k_apply_ops 475-477 -> 466-467 us, 1 484-1 487 -> 1 498-1 499
@@ -1941,8 +1692,6 @@ Scene::Scene(const SceneConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(st
     // the batch scan: 5 workgroups per CU, its occupancy (kScanWpc; 4 / 6 per CU measured slower,
     // profiles/r11_scan_ab.txt)
     compactifyGrid_ = (unsigned)numCUs_ * (unsigned)kScanWpc;
-    integrateGrid_[0] = (unsigned)std::max(1, occ0) * (unsigned)numCUs_;
-    integrateGrid_[1] = (unsigned)std::max(1, occ1) * (unsigned)numCUs_;
     BF_HIP(hipMemsetAsync(candSet_.p, 0xFF, candSet_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(blockBirth_.p, 0, blockBirth_.bytes(), stream_));
     BF_HIP(hipMemsetAsync(stats_.p, 0, stats_.bytes(), stream_));
@@ -2014,65 +1763,20 @@ void Scene::beginOp() {
     BF_LAUNCH_CHECK();
 }
 
-void Scene::alloc(const float* depth, const BFDepthCameraParams& cam, const uint32_t* bitMask) {
-    HashArgs A = make_args(cfg_, hash_.p, heap_.p, voxels_.p, blockPos_.p, blockCount_.p, visible_.p, ctrl_.p, stats_.p, bitMask);
-    set_camera_recips(A, cam);
-    dim3 g(div_up(cam.imageWidth, ALLOC_TILE), div_up(cam.imageHeight, ALLOC_TILE));
-    k_alloc_collect<<<g, 256, 0, stream_>>>(A, depth, cam, T_, Tinv_, cand_.p, cfg_.candCapacity);
-    hostPixels_ += (uint64_t)cam.imageWidth * cam.imageHeight;
-    BF_LAUNCH_CHECK();
-    // few candidates per op in steady state: a small grid keeps the last-workgroup ticket cheap
-    const unsigned grid = 64;
-    k_alloc_insert<<<grid, 256, 0, stream_>>>(A, cand_.p, cfg_.candCapacity, candSet_.p, candSetMask_, candSlot_.p, ovf_.p);
-    BF_LAUNCH_CHECK();
-    // k_alloc_insert's last workgroup runs the serial collision-list inserts; the dedup-set
-    // cleanup runs inside the following k_compactify
-}
-
 void Scene::compactify(const BFMat4& T, const BFDepthCameraParams& cam) {
     T_ = T;
     Tinv_ = mat4_inverse(T);
     beginOp();
     HashArgs A = make_args(cfg_, hash_.p, heap_.p, voxels_.p, blockPos_.p, blockCount_.p, visible_.p, ctrl_.p, stats_.p, nullptr);
-    k_compactify<CM_FRUSTUM><<<(unsigned)numCUs_ * 4, 256, 0, stream_>>>(A, cam, Tinv_, 0u, nullptr, nullptr);
+    k_compactify<<<(unsigned)numCUs_ * 4, 256, 0, stream_>>>(A, cam, Tinv_);
     BF_LAUNCH_CHECK();
 }
 
-// CUDASceneRepHashSDF::integrate (.h:65-83) / deIntegrate (.h:85-108)
+// CUDASceneRepHashSDF::integrate (.h:65-83) / deIntegrate (.h:85-108): a one-op batch
 void Scene::integrate(const BFMat4& T, const float* depth, const uint8_t* color, const BFDepthCameraParams& cam, bool deint,
                       const uint32_t* bitMask) {
-    BF_REQUIRE(depth != nullptr, BF_ERR_ARG, "depth is null");
-    T_ = T;
-    Tinv_ = mat4_inverse(T);
-    const uint32_t tw = div_up(cam.imageWidth, DEPTH_TILE), th = div_up(cam.imageHeight, DEPTH_TILE);
-    const uint32_t tw2 = div_up(cam.imageWidth, DEPTH_TILE2), th2 = div_up(cam.imageHeight, DEPTH_TILE2);
-    ensureTiles(tw * th, tw2 * th2);
-    k_begin_op_tiles<<<div_up((size_t)(tw * th + tw2 * th2) * 64, 256), 256, 0, stream_>>>(
-        ctrl_.p, stats_.p, depth, cam.imageWidth, cam.imageHeight, tw, th, tw2, th2, cfg_.hp.maxIntegrationDistance, tiles_.p,
-        tiles2_.p, 1u);
-    BF_LAUNCH_CHECK();
-    if (!deint) alloc(depth, cam, bitMask);
-    HashArgs A = make_args(cfg_, hash_.p, heap_.p, voxels_.p, blockPos_.p, blockCount_.p, visible_.p, ctrl_.p, stats_.p, bitMask);
-    A.band = band_.p;
-    A.tiles = tiles_.p;
-    A.tilesW = tw;
-    A.tilesH = th;
-    A.tiles2 = tiles2_.p;
-    A.tiles2W = tw2;
-    const unsigned grid = (unsigned)numCUs_ * 4;
-    k_compactify<CM_INTEGRATE><<<grid, 256, 0, stream_>>>(A, cam, Tinv_, cfg_.candCapacity, candSlot_.p, candSet_.p);
-    BF_LAUNCH_CHECK();
-    const unsigned igrid = deint ? integrateGrid_[1] : integrateGrid_[0];
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool timed = integrateClock_.enabled();
-    if (timed) integrateClock_.slot(ev0, ev1);
-    const uint32_t* col = reinterpret_cast<const uint32_t*>(color);
-    if (deint)
-        hipExtLaunchKernelGGL(k_integrate<true, 4>, dim3(igrid), dim3(256), 0, stream_, ev0, ev1, 0, A, depth, col, cam, Tinv_);
-    else
-        hipExtLaunchKernelGGL(k_integrate<false, 4>, dim3(igrid), dim3(256), 0, stream_, ev0, ev1, 0, A, depth, col, cam, Tinv_);
-    BF_LAUNCH_CHECK();
-    if (timed) integrateClock_.commit();
+    const VoxelOp op{T, depth, color, deint};
+    applyOps(&op, 1, cam, bitMask);
 }
 
 // reintegrate() fix of one frame (DepthSensing.cpp:890-895): deIntegrate(Told) + integrate(Tnew) as a
@@ -2087,7 +1791,7 @@ void Scene::reintegrate(const BFMat4& Told, const BFMat4& Tnew, const float* dep
 }
 
 // reintegrate() (DepthSensing.cpp:854-902) fixes of one frame as one pass: see tsdf.h
-void Scene::applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& cam) {
+void Scene::applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& cam, const uint32_t* bitMask) {
     if (n == 0) return;
     BF_REQUIRE(n <= kMaxOps, BF_ERR_ARG, "too many ops in one batch");
     OpTable tab;
@@ -2136,7 +1840,7 @@ void Scene::applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& 
     k_begin_ops_tiles<<<tileGrid, 256, 0, stream_>>>(
         ctrl_.p, stats_.p, tab, cam.imageWidth, cam.imageHeight, tw, th, tw2, th2, cfg_.hp.maxIntegrationDistance, tileBlocks);
     BF_LAUNCH_CHECK();
-    HashArgs A = make_args(cfg_, hash_.p, heap_.p, voxels_.p, blockPos_.p, blockCount_.p, visible_.p, ctrl_.p, stats_.p, nullptr);
+    HashArgs A = make_args(cfg_, hash_.p, heap_.p, voxels_.p, blockPos_.p, blockCount_.p, visible_.p, ctrl_.p, stats_.p, bitMask);
     set_camera_recips(A, cam);
     if (++batchEpoch_ >= (1u << 24)) {  // birth stamps are epoch << 8: restart the epochs before they wrap
         BF_HIP(hipMemsetAsync(blockBirth_.p, 0, blockBirth_.bytes(), stream_));
@@ -2154,10 +1858,7 @@ void Scene::applyOps(const VoxelOp* ops, uint32_t n, const BFDepthCameraParams& 
         BF_LAUNCH_CHECK();
     }
     A.band = band_.p;
-    A.tiles = tiles_.p;
     A.tilesW = tw;
-    A.tilesH = th;
-    A.tiles2 = tiles2_.p;
     A.tiles2W = tw2;
     k_compactify_ops<<<compactifyGrid_, 256, 0, stream_>>>(A, cam, tab, cfg_.candCapacity, candSlot_.p, candSet_.p,
                                                                   reinterpret_cast<OpMask*>(blockMask_.p), blockBirth_.p, epoch, B_);

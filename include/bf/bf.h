@@ -326,7 +326,7 @@ typedef struct BFReconOptions {
     int32_t useLocalDense;       /* SBA::m_bUseLocalDense = true */
     uint32_t cacheWidth, cacheHeight;  /* 80 x 60 */
     float cacheIntrinsics[4];    /* fx fy mx my of the cache resolution */
-    int32_t enableTiming;        /* record k_integrate / solve device times (bench) */
+    int32_t enableTiming;        /* record k_apply_ops / solve device times (bench) */
     int32_t recordOps;           /* keep a log of every scene call (parity replay in tests) */
     int32_t asyncBundling;       /* 1: solves run on their own stream and their poses are picked up
                                     by the frame loop when ready (the reference's bundling thread);
@@ -357,11 +357,11 @@ typedef struct BFReconStats {
     uint64_t globalGnIterations, globalPcgIterations;
     uint64_t localGnIterations, localPcgIterations;
     uint64_t removedPairs;       /* max-residual removals */
-    uint64_t integrateLaunches;  /* timed k_integrate launches */
-    double integrateKernelMs;    /* summed device time of those launches */
+    uint64_t integrateLaunches;  /* always 0 since the frame route was removed; kept for layout */
+    double integrateKernelMs;    /* always 0 since the frame route was removed; kept for layout */
     double localSolveMs, globalSolveMs;  /* summed device time of the solves */
-    uint64_t reintegrateLaunches;  /* timed k_reintegrate launches (fused de-/re-integration) */
-    double reintegrateKernelMs;
+    uint64_t reintegrateLaunches;  /* timed k_apply_ops launches (every voxel op batch: new frames and fixes) */
+    double reintegrateKernelMs;    /* summed device time of those launches */
     uint64_t localVerifications; /* local solves whose dense verification ran (useVerification) */
     uint64_t invalidLocals;      /* local submaps invalidated by it */
     uint64_t endSolves;          /* end-of-sequence global solves (bf_recon_end_solve) */

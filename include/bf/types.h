@@ -180,11 +180,15 @@ typedef struct BFTsdfStats {
     uint64_t gcBlocks;        /* blocks whose weights were scanned by GC */
     uint64_t gcFreed;         /* blocks freed by GC */
     uint64_t allocOverflow;   /* candidates dropped: candidate buffer / heap exhausted */
-    uint64_t integrateOps;    /* integrate + de-integrate calls */
-    uint64_t bandBlocks;      /* blocks on the voxel-update work lists (band-culled) */
+    uint64_t integrateOps;    /* integrate + de-integrate ops */
+    uint64_t bandBlocks;      /* blocks on the voxel-update work lists: always the half-block band cull's list (a
+                                 block some op reaches in one of its z-halves); for a single op it may be smaller
+                                 than the list of a whole-block cull */
     uint64_t voxelsRMW;       /* voxels read-modify-written by the update passes (a fused re-integration
                                  applies two updates to a voxel in one read + write) */
-    /* the op-batch pass alone (bf_scene_apply_ops / k_apply_ops), also counted in the totals above */
+    /* the op-batch pass (k_apply_ops), also counted in the totals above. Every voxel op goes through a batch
+       (bf_scene_integrate / bf_scene_deintegrate are one-op batches), so batchOps == integrateOps and these
+       fields count bf_scene_integrate too */
     uint64_t batchOps;        /* voxel ops applied through batches */
     uint64_t batchBlocks;     /* work-list blocks of the batch passes */
     uint64_t batchVoxelsRMW;  /* voxels read + written once by a batch pass */

@@ -188,7 +188,7 @@ def test_golden_fixture():
 
 
 def test_integer_colour_blend_is_exact():
-    """csrc/tsdf.hip blend_channel: the integrate colour update u8(clamp(roundf(0.2f cu + 0.8f oc),
+    """The integrate colour update u8(clamp(roundf(0.2f cu + 0.8f oc),
     0, 254.5)) (CUDASceneRepHashSDF.cu:486-496, float32, no contraction) equals the integer form
     min(((2 cu + 8 oc + 5) * 6554) >> 16, 254) for all 65536 (cu, oc)."""
     import numpy as np
@@ -205,10 +205,10 @@ def test_integer_colour_blend_is_exact():
 
 
 def test_packed_float_colour_blend_is_exact():
-    """csrc/tsdf.hip blend_color_f (the batch pass's integrate colour): min(rint((4 oc + cu) * 0.2f), 254)
+    """csrc/tsdf.hip blend_color_f (the voxel pass's integrate colour): min(rint((4 oc + cu) * 0.2f), 254)
     in float32 (4 oc + cu an exact integer, one rounded multiply, round-to-nearest-even; v_cvt_pk_u8_f32
     then converts an integral value) equals the reference byte for all 65536 (cu, oc), and an empty voxel
-    (oc := cu) gives min(cu, 254) as the reference's new-colour branch clamped like blend_channel."""
+    (oc := cu) gives min(cu, 254), the reference's new-colour branch under the same clamp."""
     import numpy as np
     f32 = np.float32
     cu = np.arange(256, dtype=f32)[:, None]

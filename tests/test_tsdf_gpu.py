@@ -22,6 +22,13 @@ def small_cam():
     return bfa.depth_camera(160, 120, fx=577.87 / 4, fy=577.87 / 4)
 
 
+# the BFTsdfStats fields oracle/tsdf.cpp fills, except `candidates`: the oracle counts distinct absent blocks, the
+# alloc walk every emission of its per-tile sets (a block that two pixel tiles reach is emitted by both), so the
+# GPU's count is larger (5 975 to 5 979 against 5 665 for test_single_frame_parity's frame)
+ORACLE_STATS = ("pixels", "allocated", "scanned", "visible", "voxelsUpdated", "gcBlocks", "gcFreed", "allocOverflow",
+                "integrateOps")
+
+
 def test_single_frame_parity(scene):
     cam = small_cam()
     p = bfa.hash_params(voxel_size=0.01, num_buckets=1 << 17, num_blocks=1 << 16)
@@ -33,6 +40,45 @@ def test_single_frame_parity(scene):
     assert pair.gpu.getHeapFreeCount() == pair.ora.getHeapFreeCount()
     assert pair.gpu.numVisible() == pair.ora.numOccupied()
     assert pair.gpu.errorFlags() == 0
+    # the device counters the oracle keeps too (oracle/tsdf.cpp), over the same one op
+    gs, os_ = pair.gpu.stats(), pair.ora.stats()
+    for f in ORACLE_STATS:
+        assert gs[f] == os_[f], f"stats field {f}: gpu {gs[f]} != oracle {os_[f]}"
+
+
+def test_streaming_mask_gates_allocation_only(scene):
+    """The reference's streaming bit mask (isSDFBlockStreamedOut, one bit per chunk of the 257^3 grid of
+    1 m chunks from -128) passed to integrate / deIntegrate: a set bit keeps the alloc walk from
+    allocating the chunk's blocks and changes nothing else."""
+    from oracle_lib import blocks_of
+    cam = small_cam()
+    p = bfa.hash_params(voxel_size=0.01, num_buckets=1 << 17, num_blocks=1 << 16)
+    (T, d, c), = render_frames(scene, cam, [0])
+    words = -(-257 ** 3 // 32)
+    assert words == 530457
+    pair = Pair(p, cam)
+    pair.ora.integrate(T, d, c, cam)  # the oracle has no mask
+    # every block the walk can test lies inside the grid the mask covers (one outside would index past it)
+    blocks = np.array(sorted(blocks_of(pair.ora.export()[0])), np.int64)
+    assert len(blocks) > 500 and np.all(np.abs(blocks) * 8 * p.virtualVoxelSize <= 100.0)
+    ones = bfa.DeviceArray.from_host(np.full(words, 0xFFFFFFFF, np.uint32))
+    zeros = bfa.DeviceArray.from_host(np.zeros(words, np.uint32))
+    dd, cc = pair._upload(0, d, c)
+
+    g = bfa.SceneRepHashSDF(p)  # every chunk streamed out: nothing is allocated
+    g.integrate(T, dd, cc, cam, bitmask=ones)
+    assert g.getHeapFreeCount() == p.numSDFBlocks
+    assert g.errorFlags() == 0
+    assert not np.any(g.export()[0]["ptr"] != bfa.abi.FREE_ENTRY)
+
+    pair.gpu.integrate(T, dd, cc, cam, bitmask=zeros)  # no chunk streamed out: the plain integrate
+    assert pair.compare() > 500
+
+    pair.gpu.deIntegrate(T, dd, cc, cam, bitmask=ones)  # the mask gates allocation only
+    pair.ora.integrate(T, d, c, cam, deintegrate=True)
+    pair.gc()
+    pair.compare()
+    assert pair.gpu.getHeapFreeCount() == p.numSDFBlocks
 
 
 def test_sequence_integrate_deintegrate_gc(scene):

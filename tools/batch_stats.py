@@ -19,7 +19,7 @@ pair = Pair(p, cam)
 frames = render_frames(scene, cam, list(range(0, 40, 4)))
 for k, (T, d, c) in enumerate(frames):
     dd, cc = pair._upload(k, d, c)
-    pair.gpu.integrate(T, dd, cc, cam)  # the GPU side only
+    pair.gpu.integrate(T, dd, cc, cam)  # the GPU side only (one-op batches: they count in the batch* fields too)
 rng = np.random.default_rng(5)
 dev = []
 for k, (T, d, c) in enumerate(frames):

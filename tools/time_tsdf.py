@@ -1,5 +1,7 @@
-"""Quick timing probe: integrate a synthetic 640x480 stream at 4 mm on the GPU and print
-per-op times and the device counters (development tool; bench.py is the contract)."""
+"""Quick timing probe: integrate a synthetic 640x480 stream at 4 mm on the GPU through
+bf_scene_integrate / bf_scene_deintegrate (each call a one-op batch: the scene's own tile and
+dc scratch, no caller cache) and print per-op times and the device counters (development tool;
+bench.py is the contract)."""
 import ctypes as C
 import os
 import sys
