@@ -226,7 +226,7 @@ class BFSiftKeyPoint(C.Structure):  # include/bf/types.h, SIFTKeyPoint
 class BFMatcherOptions(C.Structure):  # include/bf/types.h: the sparse matcher (bf_matcher_*)
     _fields_ = [("maxImages", C.c_uint32), ("maxKeysPerImage", C.c_uint32), ("matchThresh", C.c_float),
                 ("ratioMax", C.c_float), ("minNumMatches", C.c_uint32), ("maxKabschRes2", C.c_float),
-                ("intrinsicsInv", C.c_float * 16), ("reserved", C.c_uint32 * 2)]
+                ("intrinsicsInv", C.c_float * 16), ("fuseMaxCorr", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class BFMatchVerifyOptions(C.Structure):  # include/bf/types.h: the surface-area / dense-verify filters (0 = default)

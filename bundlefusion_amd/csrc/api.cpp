@@ -1372,6 +1372,26 @@ int bf_match_debug_set_filtered(bf_matcher* m, uint32_t prev, uint32_t count, co
     m->m->debugSetFiltered(prev, count, idx);
     BF_CATCH
 }
+int bf_match_fuse_to_global(bf_matcher* local, bf_matcher* global, const BFEntryJ* corr, const uint32_t* keyIdx, uint32_t nCorr,
+                              const float* transforms, const float intrinsics[16], uint32_t* index, uint32_t* numKeys,
+                              uint32_t* numTracks) {
+    BF_TRY
+    BF_REQUIRE(local && global, BF_ERR_ARG, "null matcher");
+    local->m->fuseToGlobal(*global->m, corr, keyIdx, nCorr, transforms, intrinsics, index, numKeys, numTracks);
+    BF_CATCH
+}
+int bf_match_fuse_tracks(bf_matcher* local, uint32_t* root, uint32_t* rank, uint8_t* good) {
+    BF_TRY
+    BF_REQUIRE(local, BF_ERR_ARG, "null matcher");
+    local->m->fuseTracks(root, rank, good);
+    BF_CATCH
+}
+int bf_match_image_keys(bf_matcher* m, uint32_t image, BFSiftKeyPoint* keys, uint8_t* descs) {
+    BF_TRY
+    BF_REQUIRE(m, BF_ERR_ARG, "null matcher");
+    m->m->imageKeys(image, keys, descs);
+    BF_CATCH
+}
 int bf_matcher_synchronize(bf_matcher* m) {
     BF_TRY
     BF_REQUIRE(m, BF_ERR_ARG, "null matcher");

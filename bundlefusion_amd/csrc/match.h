@@ -19,6 +19,7 @@ struct MatcherConfig {
     uint32_t minNumMatches = 5;
     float maxKabschRes2 = 0.0004f;
     float kinv[16] = {};
+    uint32_t fuseMaxCorr = 0;  // records a fuseToGlobal FROM this matcher may take; 0: no fuse scratch, no fusing
 };
 
 // thresholds of the surface-area and dense-verify filters (zParametersBundlingDefault.txt / zParametersDefault.txt)
@@ -69,8 +70,15 @@ public:
     void transforms(uint32_t prev, float* T, float* Tinv);
     void debugDots(uint32_t prev, uint32_t cur, const uint32_t* rows, uint32_t nRows, const uint32_t* cols, uint32_t nCols,
                    int32_t* dots, int32_t* rowStats);
+    // match_fuse.h: this store's tracks become the next image of glob's store; queued on this matcher's stream, glob's
+    // stream ordered behind it, returns after the read-back of the counts
+    void fuseToGlobal(Matcher& glob, const BFEntryJ* corr, const uint32_t* keyIdx, uint32_t nCorr, const float* transforms,
+                      const float* intrinsics, uint32_t* index, uint32_t* numKeys, uint32_t* numTracks);
+    void fuseTracks(uint32_t* root, uint32_t* rank, uint8_t* good);
+    void imageKeys(uint32_t image, BFSiftKeyPoint* keys, uint8_t* descs);
 
 private:
+    uint32_t appendStored(uint32_t n);  // the bookkeeping of addImage for n keys already in place behind the last image
     void uploadTable();
     void launchMatch(uint32_t cur, uint32_t start, uint32_t pairs, bool debug, uint32_t nRows, uint32_t nCols);
 
@@ -97,6 +105,17 @@ private:
     uint32_t* hostTable_ = nullptr;          // pinned, 4 * maxImages
     uint32_t* hostCounts_ = nullptr;         // pinned, maxImages
     uint32_t* hostBase_ = nullptr;           // pinned, maxImages
+    // key fusing (match_fuse.h), allocated when cfg.fuseMaxCorr > 0
+    DevBuf<uint32_t> fuseCnt_, fuseOff_, fusePar_, fuseRoot_, fuseRank_;  // per key
+    DevBuf<uint8_t> fuseGood_, fuseEdge_;                                 // per key, per record
+    DevBuf<uint32_t> fuseAdj_, fuseAdjT_;                                 // per half-edge
+    DevBuf<uint32_t> fuseComp_, fuseRep_, fuseOutRep_;                    // per component / fused key
+    DevBuf<BFSiftKeyPoint> fuseCompKey_, fuseOutKey_;
+    DevBuf<uint32_t> fuseCounts_;                                         // {tracks, keys stored, error bits, components}
+    uint32_t* hostFuse_ = nullptr;                                        // pinned, 4
+    hipEvent_t fuseDone_ = nullptr;
+    uint32_t fuseKeys_ = 0;  // keys in use at the last fuse
+    bool fuseRan_ = false;
 };
 
 }  // namespace bf

@@ -5,7 +5,7 @@
 //   SiftGPU/SIFTImageManager.cu:59-607, 610-687, SiftGPU/SIFTImageManager.cpp:44-83, 551-575,
 //   SiftGPU/cuda_kabsch.h:73-229, 281-502, SiftGPU/cuda_surfaceArea.h, SiftGPU/cuda_SVD.h:17-213,
 //   SiftGPU/cuda_EigenValue.h:56-85.
-// The DoG detector / descriptor, tryRevalidation and fuseToGlobal are not here.
+// The DoG detector / descriptor and tryRevalidation are not here; fuseToGlobal is match_fuse.h, included at the end.
 //
 // k_match — one workgroup (4 waves) per image pair (prev, cur), every pair of a call in one launch. The reference
 // writes the num1 x num2 int32 dot matrix to memory and reduces it with two more kernels per pair; here it never
@@ -1007,6 +1007,8 @@ MatcherConfig make_matcher_config(const BFMatcherOptions* o) {
     }
     if (!any)
         for (int k = 0; k < 16; k++) c.kinv[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+    BF_REQUIRE(o->fuseMaxCorr <= (1u << 28), BF_ERR_ARG, "fuseMaxCorr above 2^28");
+    c.fuseMaxCorr = o->fuseMaxCorr;
     return c;
 }
 
@@ -1033,6 +1035,26 @@ Matcher::Matcher(const MatcherConfig& cfg, hipStream_t stream) : cfg_(cfg), stre
     BF_HIP(hipHostMalloc((void**)&hostTable_, 4 * n * sizeof(uint32_t), hipHostMallocDefault));
     BF_HIP(hipHostMalloc((void**)&hostCounts_, n * sizeof(uint32_t), hipHostMallocDefault));
     BF_HIP(hipHostMalloc((void**)&hostBase_, (n + 16) * sizeof(uint32_t), hipHostMallocDefault));
+    if (cfg.fuseMaxCorr) {
+        const size_t rec = cfg.fuseMaxCorr, comps = keys < rec ? keys : rec;  // a component holds a record of its own
+        fuseCnt_.alloc(keys);
+        fuseOff_.alloc(keys + 1);
+        fusePar_.alloc(keys);
+        fuseRoot_.alloc(keys);
+        fuseRank_.alloc(keys);
+        fuseGood_.alloc(keys);
+        fuseEdge_.alloc(rec);
+        fuseAdj_.alloc(2 * rec);
+        fuseAdjT_.alloc(2 * rec);
+        fuseComp_.alloc(comps);
+        fuseRep_.alloc(comps);
+        fuseOutRep_.alloc(comps);
+        fuseCompKey_.alloc(comps);
+        fuseOutKey_.alloc(comps);
+        fuseCounts_.alloc(4);
+        BF_HIP(hipHostMalloc((void**)&hostFuse_, 4 * sizeof(uint32_t), hipHostMallocDefault));
+        BF_HIP(hipEventCreateWithFlags(&fuseDone_, hipEventDisableTiming));
+    }
     BF_HIP(hipFuncSetAttribute((const void*)k_match<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MATCH_LDS_BYTES));
     BF_HIP(hipFuncSetAttribute((const void*)k_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MATCH_LDS_BYTES));
     std::memcpy(hostBase_ + n, cfg_.kinv, 64);
@@ -1044,6 +1066,8 @@ Matcher::~Matcher() {
     if (hostTable_) (void)hipHostFree(hostTable_);
     if (hostCounts_) (void)hipHostFree(hostCounts_);
     if (hostBase_) (void)hipHostFree(hostBase_);
+    if (hostFuse_) (void)hipHostFree(hostFuse_);
+    if (fuseDone_) (void)hipEventDestroy(fuseDone_);
 }
 
 void Matcher::reset() {
@@ -1052,6 +1076,7 @@ void Matcher::reset() {
     valid_.clear();
     totalKeys_ = 0;
     tableDirty_ = true;
+    fuseRan_ = false;
     const size_t n = cfg_.maxImages;
     BF_HIP(hipMemsetAsync(rawCount_.p, 0, n * 4, stream_));
     BF_HIP(hipMemsetAsync(filtCount_.p, 0, n * 4, stream_));
@@ -1069,13 +1094,17 @@ uint32_t Matcher::addImage(const BFSiftKeyPoint* keys, const uint8_t* descs, uin
     BF_REQUIRE(n <= cfg_.maxKeys, BF_ERR_ARG, "more keys than maxKeysPerImage");
     BF_REQUIRE(n == 0 || (keys && descs), BF_ERR_ARG, "null keys / descriptors");
     BF_REQUIRE(num_.size() < cfg_.maxImages, BF_ERR_CAPACITY, "matcher image store is full");
-    const uint32_t index = (uint32_t)num_.size();
     if (n) {
         BF_HIP(hipMemcpyAsync(keys_.p + totalKeys_, keys, (size_t)n * sizeof(BFSiftKeyPoint), hipMemcpyDeviceToDevice, stream_));
         BF_HIP(hipMemcpyAsync(descs_.p + (size_t)totalKeys_ * 128, descs, (size_t)n * 128, hipMemcpyDeviceToDevice, stream_));
         k_desc_sums<<<div_up(n, 128), 128, 0, stream_>>>(descs_.p, sums_.p, totalKeys_, n);
         BF_LAUNCH_CHECK();
     }
+    return appendStored(n);
+}
+
+uint32_t Matcher::appendStored(uint32_t n) {
+    const uint32_t index = (uint32_t)num_.size();
     num_.push_back(n);
     off_.push_back(totalKeys_);
     valid_.push_back(index == 0 ? 1 : 0);  // image 0 starts valid; filterFrames decides the others
@@ -1318,6 +1347,15 @@ void Matcher::filteredMatches(uint32_t prev, uint32_t* count, uint32_t* idx, flo
     if (dist) BF_HIP(hipMemcpy(dist, filtDist_.p + (size_t)prev * kFilt, 4 * kFilt, hipMemcpyDeviceToHost));
 }
 
+void Matcher::imageKeys(uint32_t image, BFSiftKeyPoint* keys, uint8_t* descs) {
+    BF_REQUIRE(image < numImages(), BF_ERR_ARG, "image >= numImages");
+    BF_HIP(hipStreamSynchronize(stream_));
+    const size_t n = num_[image], at = off_[image];
+    if (n == 0) return;
+    if (keys) BF_HIP(hipMemcpy(keys, keys_.p + at, n * sizeof(BFSiftKeyPoint), hipMemcpyDeviceToHost));
+    if (descs) BF_HIP(hipMemcpy(descs, descs_.p + at * 128, n * 128, hipMemcpyDeviceToHost));
+}
+
 void Matcher::transforms(uint32_t prev, float* T, float* Tinv) {
     BF_REQUIRE(prev < numImages(), BF_ERR_ARG, "prev >= numImages");
     BF_HIP(hipStreamSynchronize(stream_));
@@ -1346,3 +1384,5 @@ void Matcher::debugDots(uint32_t prev, uint32_t cur, const uint32_t* rows, uint3
 }
 
 }  // namespace bf
+
+#include "match_fuse.h"

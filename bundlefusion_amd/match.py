@@ -15,10 +15,11 @@ NO_FRAME = 0xFFFFFFFF
 
 
 def matcher_options(max_images: int, max_keys_per_image: int = 1024, intrinsics_inv=None, match_thresh=0.7,
-                    ratio_max=0.8, min_num_matches=5, max_kabsch_res2=0.0004) -> BFMatcherOptions:
-    """Defaults are zParametersBundlingDefault.txt's; intrinsics_inv: row-major 4x4 inverse colour intrinsics."""
+                    ratio_max=0.8, min_num_matches=5, max_kabsch_res2=0.0004, fuse_max_corr=0) -> BFMatcherOptions:
+    """Defaults are zParametersBundlingDefault.txt's; intrinsics_inv: row-major 4x4 inverse colour intrinsics;
+    fuse_max_corr: the most records a fuse_to_global from this matcher takes (0: it cannot be fused from)."""
     o = BFMatcherOptions()
-    o.maxImages, o.maxKeysPerImage = max_images, max_keys_per_image
+    o.maxImages, o.maxKeysPerImage, o.fuseMaxCorr = max_images, max_keys_per_image, fuse_max_corr
     o.matchThresh, o.ratioMax, o.minNumMatches, o.maxKabschRes2 = match_thresh, ratio_max, min_num_matches, max_kabsch_res2
     k = np.eye(4, dtype=np.float32) if intrinsics_inv is None else np.asarray(intrinsics_inv, np.float32).reshape(4, 4)
     o.intrinsicsInv[:] = k.ravel().tolist()
@@ -200,6 +201,42 @@ class Matcher:
                 np.zeros((0, 2), np.uint32)
             return res, total.value, k
         return res, total.value
+
+    def fuse_to_global(self, glob: "Matcher", corr, key_idx, n: int, transforms, intrinsics):
+        """SIFTImageManager::fuseToGlobal: this (local) store's tracks become the next image of `glob`.
+        corr: EntryJ [>= n], key_idx: uint32 [>= n, 2], transforms: float32 [images, 4, 4] (frame -> first frame), each a
+        DeviceArray or a host array (uploaded); intrinsics: host row-major 4x4 colour intrinsics.
+        Returns (image index in glob, keys stored, fused keys before the cut to maxKeysPerImage)."""
+        def dev(a, dtype):
+            return a if isinstance(a, DeviceArray) or a is None else DeviceArray.from_host(np.ascontiguousarray(a, dtype))
+        n = int(n)
+        d_corr = dev(corr if n else None, ENTRYJ_DTYPE)
+        d_idx = dev(key_idx if n else None, np.uint32)
+        d_T = dev(transforms, np.float32)
+        K = np.ascontiguousarray(np.asarray(intrinsics, np.float32).reshape(16))
+        idx, keys, tracks = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().bf_match_fuse_to_global(self.h, glob.h, d_corr.ptr if d_corr is not None else None,
+                                            d_idx.ptr if d_idx is not None else None, C.c_uint32(n),
+                                            d_T.ptr if d_T is not None else None, K.ctypes.data_as(C.c_void_p),
+                                            C.byref(idx), C.byref(keys), C.byref(tracks)))
+        return idx.value, keys.value, tracks.value
+
+    def fuse_tracks(self):
+        """(root, rank, good) per key of this store as the last fuse_to_global from it left them: the lowest key of the
+        key's component (NO_FRAME for a key in no track), its position in the track (NO_FRAME), its flag."""
+        n = sum(self.num_keys(i)[0] for i in range(self.num_images()))
+        root, rank, good = np.full(n, NO_FRAME, np.uint32), np.full(n, NO_FRAME, np.uint32), np.zeros(n, np.uint8)
+        check(lib().bf_match_fuse_tracks(self.h, root.ctypes.data_as(C.c_void_p), rank.ctypes.data_as(C.c_void_p),
+                                         good.ctypes.data_as(C.c_void_p)))
+        return root, rank, good
+
+    def image_keys(self, image: int):
+        """(keys [n] SIFT_KEYPOINT_DTYPE, descs [n, 128] uint8) of a stored image, read back to the host."""
+        n = self.num_keys(image)[0]
+        keys, descs = np.empty(n, SIFT_KEYPOINT_DTYPE), np.empty((n, 128), np.uint8)
+        check(lib().bf_match_image_keys(self.h, C.c_uint32(image), keys.ctypes.data_as(C.c_void_p),
+                                        descs.ctypes.data_as(C.c_void_p)))
+        return keys, descs
 
     def _matches(self, fn, prev: int, cap: int):
         count = C.c_uint32()

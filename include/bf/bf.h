@@ -31,7 +31,9 @@ extern "C" {
                              bf_recon_set_render (visualizeFrame's render per frame);
                              additive, still 4: the sparse matcher (BFSiftKeyPoint, BFMatcherOptions, bf_matcher_*);
                              additive, still 4: its surface-area and dense-verify filters (BFMatchVerifyOptions, bf_match_*);
-                             additive, still 4: the SIFT detector (BFSiftOptions, bf_sift_*) */
+                             additive, still 4: the SIFT detector (BFSiftOptions, bf_sift_*);
+                             additive, still 4: key fusing (BFMatcherOptions.fuseMaxCorr in place of reserved[0],
+                             bf_match_fuse_to_global, bf_match_fuse_tracks, bf_match_image_keys) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -606,8 +608,9 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
 
 /* ---- sparse matcher: the matching side of SIFTImageManager + SiftMatch + Bundler::matchAndFilter ----------
  * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out, through the reference's whole
- * filter chain: Kabsch, surface area, dense verify, filterFrames (the DoG detector / descriptor is bf_sift_* below;
- * tryRevalidation and fuseToGlobal are not part of it).
+ * filter chain: Kabsch, surface area, dense verify, filterFrames, and a solved submap's tracks fused into the keys of
+ * its global image (bf_match_fuse_to_global). The DoG detector / descriptor is bf_sift_* below; tryRevalidation is not
+ * part of it.
  * Work is queued on the matcher's own stream; the read-backs and bf_matcher_filter_frames / _add_to_residuals
  * wait for it. No device allocation after bf_matcher_create. Per-pair results are indexed by the earlier image
  * `prev`, as the reference's d_curr* arrays are, and hold the last bf_matcher_match / _filter.
@@ -622,6 +625,10 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
  * A second one, in bf_match_filter_dense_verify: the reference adds its warps' partial sums of a pair with shared-memory
  * float atomicAdd, in race order. Here they are added in a fixed order (pixels per thread, a wave tree, the waves, the
  * row slices), so the sums and the verdicts that hinge on them are bit-deterministic.
+ *
+ * A third one, in bf_match_fuse_to_global: with more fused keys than maxKeysPerImage the reference sorts the key points
+ * by depth and leaves the descriptor array as it was, so keys and descriptors come apart (SIFTImageManager.cpp:459-467).
+ * Here the order is (depth ascending, track order ascending) and every descriptor moves with its key.
  *
  * The entries added for the two filters are spelled bf_match_*: they take the same bf_matcher handle. */
 typedef struct bf_matcher bf_matcher;
@@ -707,6 +714,33 @@ int bf_match_and_filter(bf_matcher* m, uint32_t curFrame, uint32_t startFrame, c
  * key array (the transforms stay), so that the two filters can be given lists the Kabsch filter never lets through,
  * such as collinear points. Synchronizes. */
 int bf_match_debug_set_filtered(bf_matcher* m, uint32_t prev, uint32_t count, const uint32_t* idx);
+/* Bundler::fuseToGlobal's sparse half: SIFTImageManager::fuseToGlobal / computeTracks / findTrack
+ * (SIFTImageManager.cpp:367-476), on the device. Every valid record (imgIdx_i != UINT32_MAX) of corr[nCorr] is an edge
+ * between the keys keyIdx[2 r], keyIdx[2 r + 1] of `local`'s store (linear key indices; DEVICE arrays in the layout
+ * bf_matcher_add_to_residuals writes and the solver invalidates in place), good when
+ * length(T[i] pos_i - T[j] pos_j) < 0.03. Keys are chained into tracks by the reference's depth-first search (roots in
+ * ascending key index, neighbours in record order, a key flagged by the edge that found it); a track's good entries
+ * are averaged in the submap's frame with transforms (DEVICE float[16 x local images], frame -> first frame),
+ * projected with intrinsics (HOST, row-major 4x4 colour intrinsics) and stored as one key {x, y, scale of the track's
+ * first entry, depth} with that entry's descriptor. The keys become the next image of `global`'s store exactly as
+ * bf_matcher_add_image would append them, in track order; more than min(maxKeysPerImage of local, of global) are cut
+ * to the nearest by (depth, track order) - the third departure above. *index = the new image's index, *numKeys = keys
+ * stored, *numTracks = fused keys before the cut (each may be NULL). nCorr = 0 appends an image without keys.
+ * Queued on local's stream; global's stream is ordered behind it by an event; returns after the read-back of the
+ * counts. corr, keyIdx and transforms must be complete before the call (their producer is synchronised by the
+ * caller). local created with fuseMaxCorr = 0, nCorr > fuseMaxCorr, global == local: BF_ERR_ARG; a full global store:
+ * BF_ERR_CAPACITY; a record whose key index is >= local's key count or whose image index is >= its image count is
+ * never dereferenced and makes the call return BF_ERR_ARG with nothing appended. */
+int bf_match_fuse_to_global(bf_matcher* local, bf_matcher* global, const BFEntryJ* corr, const uint32_t* keyIdx, uint32_t nCorr,
+                              const float* transforms, const float intrinsics[16], uint32_t* index, uint32_t* numKeys,
+                              uint32_t* numTracks);
+/* HOST read-back of the last bf_match_fuse_to_global from `local`, per key of its store at that time: root = the
+ * lowest key of the key's component (UINT32_MAX for a key in no track), rank = its position in the track (UINT32_MAX),
+ * good = 1 if the edge that found it was good (0). Any output may be NULL. No fuse since create / reset: BF_ERR_STATE. */
+int bf_match_fuse_tracks(bf_matcher* local, uint32_t* root, uint32_t* rank, uint8_t* good);
+/* HOST read-back of a stored image: keys[n], descs[n][128] with n = its key count (either may be NULL). The way to look
+ * at an image that bf_match_fuse_to_global made. Synchronizes. */
+int bf_match_image_keys(bf_matcher* m, uint32_t image, BFSiftKeyPoint* keys, uint8_t* descs);
 int bf_matcher_synchronize(bf_matcher* m);
 int bf_matcher_timer_start(bf_matcher* m, bf_timer* t);
 int bf_matcher_timer_stop(bf_matcher* m, bf_timer* t, float* ms); /* synchronizes */

@@ -303,7 +303,9 @@ typedef struct BFMatcherOptions {
     uint32_t minNumMatches;     /* s_minNumMatchesLocal / Global [5] */
     float maxKabschRes2;        /* s_maxKabschResidual2 [0.0004] */
     float intrinsicsInv[16];    /* row-major inverse colour intrinsics (m_siftIntrinsicsInv); all 0 = identity */
-    uint32_t reserved[2];
+    uint32_t fuseMaxCorr;       /* most records a bf_match_fuse_to_global FROM this matcher takes (<= 2^28); 0: no fuse
+                                   scratch is allocated and fusing from it is BF_ERR_ARG (was reserved[0]) */
+    uint32_t reserved;
 } BFMatcherOptions;
 
 /* Thresholds of the matcher's surface-area and dense-verify filters (bf_match_filter_*); the values of
