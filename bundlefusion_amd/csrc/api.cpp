@@ -39,6 +39,7 @@ uint32_t synth_correspondences(const BFSynthScene& sc, const float* poses, uint3
                                BFEntryJ* out, uint32_t cap);
 void synth_cache_frame(const BFSynthScene& sc, const BFMat4& T, const BFDepthCameraParams& cam, float* depth, float* campos,
                        float* normals, uint8_t* normalsU8, float* intensity, float* intensityDeriv);
+void debug_wg_scan(const uint32_t* in, uint32_t n, uint32_t wg, bool flags, uint32_t* out, uint32_t* total);
 
 // General cofactor inverse, cuda_SimpleMatrixUtil.h:980-1090 (host side of setLastRigidTransform,
 // CUDASceneRepHashSDF.h:128-134).
@@ -1486,6 +1487,11 @@ int bf_sift_debug_raw_keys(bf_sift* s, uint32_t levelIndex, int32_t* colRow, uin
     BF_TRY
     BF_REQUIRE(s, BF_ERR_ARG, "null sift detector");
     s->s->debugRawKeys(levelIndex, colRow, packedOrientations, cap, n);
+    BF_CATCH
+}
+int bf_debug_wg_scan(const uint32_t* d_in, uint32_t n, uint32_t wg, int flags, uint32_t* d_out, uint32_t* d_total) {
+    BF_TRY
+    debug_wg_scan(d_in, n, wg, flags != 0, d_out, d_total);
     BF_CATCH
 }
 int bf_sift_synchronize(bf_sift* s) {

@@ -77,26 +77,20 @@ __global__ void k_dense_overlap(BA a) {
 // The overlapping pairs in (i, j) order (the reference appends them at atomic offsets): one workgroup
 // compacts the flag matrix with wave ballots; K_NPAIRS = all pairs found, the first maxPairs are kept.
 __global__ __launch_bounds__(256) void k_dense_compact(BA a) {
-    __shared__ uint32_t sCnt[4], sBase;
+    __shared__ uint32_t sCnt[4];
     if (a.ctrl[K_GN_DONE]) return;
-    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6, NN = a.N * a.N;
-    if (threadIdx.x == 0) sBase = 0;
-    __syncthreads();
+    const uint32_t NN = a.N * a.N;
+    uint32_t base = 0;  // the same in every lane
     for (uint32_t b0 = 0; b0 < NN; b0 += 256) {
         const uint32_t idx = b0 + threadIdx.x;
         const bool f = idx < NN && a.pairFlag[idx] != 0u;
-        const unsigned long long m = __ballot(f);
-        if (lane == 0) sCnt[wv] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t off = sBase;
-        for (uint32_t w = 0; w < wv; w++) off += sCnt[w];
-        off += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        uint32_t found;
+        const uint32_t off = base + wg_compact_offset<4>(f, sCnt, found);
         if (f && off < a.maxPairs) a.pairs[off] = make_uint2(idx / a.N, idx % a.N);
-        __syncthreads();
-        if (threadIdx.x == 0) for (uint32_t w = 0; w < 4; w++) sBase += sCnt[w];
+        base += found;
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.ctrl[K_NPAIRS] = sBase;
+    if (threadIdx.x == 0) a.ctrl[K_NPAIRS] = base;
 }
 
 // FindDenseCorrespondences_Kernel (:92-160, uchar4-normal variant :152-184) + WeightDenseCorrespondences (:162-180)

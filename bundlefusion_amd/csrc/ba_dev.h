@@ -8,6 +8,7 @@
 #pragma once
 #include "ba.h"
 #include "lie.h"
+#include "wave.h"
 
 namespace bf {
 namespace {
@@ -88,7 +89,6 @@ struct BA {
     unsigned long long spinTicks;  // bound of every k_pcg_persist wait (s_memrealtime ticks, 100 MHz)
 };
 
-__device__ __forceinline__ unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ float* vptr(const BA& a, int field, uint32_t v) { return a.vec + ((size_t)field * a.maxN + v) * 8; }
 __device__ __forceinline__ void vload(const BA& a, int field, uint32_t v, f3& r, f3& t) {
     const float4* p = reinterpret_cast<const float4*>(vptr(a, field, v));
@@ -270,8 +270,6 @@ __device__ float block_sum(float v, float* sh) {
     return r;
 }
 
-// lanes of a wave below `lane`, as a ballot mask
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
 // one workgroup of WG threads: exclusive scan of in[0, n) -> out[0, n), out[n] = total (sh: WG ints)
 __device__ void block_exclusive_scan(const int* in, int* out, uint32_t n, int* sh) {
     int carry = 0;

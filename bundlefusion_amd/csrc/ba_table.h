@@ -88,7 +88,7 @@ __global__ __launch_bounds__(64) void k_tile_fill(BA a) {
     const uint32_t t = blockIdx.x, lane = threadIdx.x;
     for (uint32_t r = lane; r < a.N; r += 64) run[r] = 0;
     __syncthreads();
-    const uint64_t lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lower = lanes_below(lane);
     const uint32_t c1 = min((t + 1) * a.tile, a.nCorr);
     for (uint32_t c0 = t * a.tile; c0 < c1; c0 += 64) {
         const uint32_t c = c0 + lane;
@@ -124,31 +124,23 @@ __global__ __launch_bounds__(64) void k_tile_fill(BA a) {
 }
 // keep the entries that survived the cap (stable), rowLen = kept count
 __global__ __launch_bounds__(WG) void k_compact_rows(BA a) {
-    __shared__ int base;
+    __shared__ uint32_t cnt[WG / 64];
     const uint32_t v = blockIdx.x;
     if (v >= a.N) return;
     const int n = min(a.rowCount[v], (int)a.cap), s0 = a.rowStart[v];
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
+    uint32_t base = 0;  // the same in every lane
     for (int k0 = 0; k0 < n; k0 += WG) {
         const int k = k0 + threadIdx.x;
         bool keep = false;
         int c = 0;
         if (k < n) { c = a.rowTmp[s0 + k]; keep = corr_valid(a.corr[c]); }
-        __shared__ int cnt[WG / 64];
-        const unsigned long long m = __ballot(keep);
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) cnt[w] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int q = 0; q < w; q++) off += cnt[q];
-        const unsigned l = lane_id();
-        if (keep) a.rowIdx[s0 + off + __popcll(m & ((l == 0) ? 0ull : (~0ull >> (64 - l))))] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) { int t = 0; for (int q = 0; q < WG / 64; q++) t += cnt[q]; base += t; }
+        uint32_t kept;
+        const uint32_t off = base + wg_compact_offset<WG / 64>(keep, cnt, kept);
+        if (keep) a.rowIdx[s0 + off] = c;
+        base += kept;
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.rowLen[v] = base;
+    if (threadIdx.x == 0) a.rowLen[v] = (int)base;
 }
 
 // chunk table: row v (v >= 1; image 0 is fixed) is cut into ceil(rowLen / CH) chunks of CH entries

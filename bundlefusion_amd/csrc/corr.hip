@@ -21,6 +21,7 @@
 #include "bf_math.h"
 #include "bf_runtime.h"
 #include "corr.h"
+#include "wave.h"
 
 #include <vector>
 
@@ -56,18 +57,15 @@ struct CorrArgs {
 
 __global__ __launch_bounds__(CORR_WG) void k_corr_pairs(CorrArgs A) {
     __shared__ uint32_t sWave[CORR_WG / 64];
-    __shared__ uint32_t sTaken;
     const uint32_t p = blockIdx.x;
     const uint32_t i = A.list ? A.list[p].x : A.start + p;
     const uint32_t cur = A.list ? A.list[p].y : A.cur;
-    if (threadIdx.x == 0) sTaken = 0;
-    __syncthreads();
     const uint32_t N = A.gridW * A.gridH;
     const float* di = A.depth[i];
     const float* dj = A.depth[cur];
     const float* Ti = A.T + 16 * (size_t)i;
     const float* Tj = A.Tinv + 16 * (size_t)cur;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t taken = 0;  // the same in every lane
     for (uint32_t r = 0; r < N; r += CORR_WG) {
         const uint32_t k = r + threadIdx.x;
         bool ok = false;
@@ -97,23 +95,14 @@ __global__ __launch_bounds__(CORR_WG) void k_corr_pairs(CorrArgs A) {
             }
         }
         // keep the first valid candidates of this round in candidate order
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) sWave[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < CORR_WG / 64; w++) {
-            before += (w < wave) ? sWave[w] : 0u;
-            all += sWave[w];
-        }
-        const uint32_t taken = sTaken;
-        const uint32_t at = taken + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        uint32_t all;
+        const uint32_t at = taken + wg_compact_offset<CORR_WG / 64>(ok, sWave, all);
         if (ok && at < A.maxPerPair) A.slots[(size_t)p * A.maxPerPair + at] = e;
+        taken = min(taken + all, A.maxPerPair);
+        if (taken >= A.maxPerPair) break;  // workgroup-uniform
         __syncthreads();
-        if (threadIdx.x == 0) sTaken = min(taken + all, A.maxPerPair);
-        __syncthreads();
-        if (sTaken >= A.maxPerPair) break;  // workgroup-uniform
     }
-    if (threadIdx.x == 0) A.counts[p] = sTaken;
+    if (threadIdx.x == 0) A.counts[p] = taken;
 }
 
 // pair order: exclusive scan of the counts (one workgroup), then each thread copies its pair's slots
@@ -122,31 +111,16 @@ __global__ __launch_bounds__(1024) void k_corr_pack(const BFEntryJ* __restrict__
                                                     uint32_t pairs, uint32_t maxPerPair, uint32_t minPerPair, BFEntryJ* out,
                                                     uint32_t cap, uint32_t* total) {
     __shared__ uint32_t sWave[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;  // the same in every lane
     for (uint32_t r = 0; r < pairs; r += 1024) {
         const uint32_t p = r + threadIdx.x;
         uint32_t c = p < pairs ? counts[p] : 0u;
         if (c < minPerPair) c = 0;
-        uint32_t incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o);
-            if (lane >= (uint32_t)o) incl += t;
-        }
-        if (lane == 63) sWave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < 16; w++) {
-            before += (w < wave) ? sWave[w] : 0u;
-            all += sWave[w];
-        }
-        const uint32_t base = carry + before + incl - c;
+        uint32_t all;
+        const uint32_t base = carry + wg_exclusive_scan<16>(c, sWave, all);
         for (uint32_t k = 0; k < c; k++)
             if (base + k < cap) out[base + k] = slots[(size_t)p * maxPerPair + k];
-        __syncthreads();
-        if (threadIdx.x == 0) carry += all;
+        carry += all;
         __syncthreads();
     }
     if (threadIdx.x == 0) *total = carry;

@@ -39,6 +39,7 @@
 #include "bf_math.h"
 #include "bf_runtime.h"
 #include "match.h"
+#include "wave.h"
 
 namespace bf {
 
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(MATCH_WG) void k_match(MatchArgs A) {
     int* sColW = (int*)smem4 + LDS_DESC;
     int* sCol = sColW + LDS_COLW;
     int* sRow = sCol + LDS_COL;
-    int* sMisc = sRow + LDS_ROW;
+    uint32_t* sMisc = (uint32_t*)(sRow + LDS_ROW);  // the scan's wave totals
 
     const uint32_t prev = A.start + blockIdx.x;
     if (prev == A.cur) return;
@@ -279,18 +280,8 @@ __global__ __launch_bounds__(MATCH_WG) void k_match(MatchArgs A) {
             }
         }
     }
-    uint32_t incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += t;
-    }
-    if (lane == 63) sMisc[wave] = (int)incl;
-    __syncthreads();
-    uint32_t at = incl - mine, total = 0;
-    for (uint32_t w = 0; w < 4; w++) {
-        at += (w < wave) ? (uint32_t)sMisc[w] : 0u;
-        total += (uint32_t)sMisc[w];
-    }
+    uint32_t total;
+    uint32_t at = wg_exclusive_scan<MATCH_WG / 64>(mine, sMisc, total);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         if (fa[j] >= 0) {

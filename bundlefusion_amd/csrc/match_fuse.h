@@ -33,6 +33,7 @@
 
 #include "bf_math.h"
 #include "match.h"
+#include "wave.h"
 
 namespace bf {
 namespace {
@@ -113,32 +114,6 @@ __device__ bool fuse_unite(uint32_t* par, uint32_t a, uint32_t b, uint32_t bound
     return false;
 }
 
-// exclusive scan of one value per lane over the workgroup; *total = the sum. s: 17 words of LDS.
-__device__ uint32_t fuse_block_scan(uint32_t v, uint32_t* s, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s[w] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < FUSE_WG / 64; i++) {
-            const uint32_t t = s[i];
-            s[i] = run;
-            run += t;
-        }
-        s[FUSE_WG / 64] = run;
-    }
-    __syncthreads();
-    const uint32_t r = s[w] + incl - v;
-    *total = s[FUSE_WG / 64];
-    __syncthreads();
-    return r;
-}
-
 __device__ void fuse_sift_down(uint32_t* a, uint32_t i, uint32_t n) {
     for (;;) {
         uint32_t c = 2 * i + 1;
@@ -186,7 +161,7 @@ __device__ __forceinline__ f3 fuse_world(const FuseArgs& A, uint32_t img, const 
 }
 
 __global__ __launch_bounds__(FUSE_WG) void k_fuse(FuseArgs A) {
-    __shared__ uint32_t sScan[FUSE_WG / 64 + 1];
+    __shared__ uint32_t sScan[FUSE_WG / 64];  // every scan is followed by a fuse_sync() before the next one writes it
     const uint32_t tid = threadIdx.x, N = A.nKeys, C = A.nCorr;
     const uint32_t bound = N + 2 * C + 2;
     const uint32_t chunk = (N + FUSE_WG - 1) / FUSE_WG;  // consecutive keys per lane in the scans
@@ -228,7 +203,7 @@ __global__ __launch_bounds__(FUSE_WG) void k_fuse(FuseArgs A) {
         uint32_t sum = 0;
         for (uint32_t k = lo; k < hi; k++) sum += fuse_ld(A.cnt + k);
         uint32_t total;
-        uint32_t run = fuse_block_scan(sum, sScan, &total);
+        uint32_t run = wg_exclusive_scan<FUSE_WG / 64>(sum, sScan, total);
         for (uint32_t k = lo; k < hi; k++) {
             const uint32_t d = fuse_ld(A.cnt + k);
             A.off[k] = run;
@@ -264,7 +239,7 @@ __global__ __launch_bounds__(FUSE_WG) void k_fuse(FuseArgs A) {
     {
         uint32_t mine = 0;
         for (uint32_t k = lo; k < hi; k++) mine += A.root[k] == k;
-        uint32_t at = fuse_block_scan(mine, sScan, &nComp);
+        uint32_t at = wg_exclusive_scan<FUSE_WG / 64>(mine, sScan, nComp);
         for (uint32_t k = lo; k < hi; k++)
             if (A.root[k] == k) {
                 if (at < A.compCap) A.comp[at] = k;
@@ -348,7 +323,7 @@ __global__ __launch_bounds__(FUSE_WG) void k_fuse(FuseArgs A) {
     {
         uint32_t mine = 0;
         for (uint32_t c = clo; c < chi; c++) mine += A.rep[c] != FUSE_NONE;
-        uint32_t at = fuse_block_scan(mine, sScan, &nTracks);
+        uint32_t at = wg_exclusive_scan<FUSE_WG / 64>(mine, sScan, nTracks);
         for (uint32_t c = clo; c < chi; c++)
             if (A.rep[c] != FUSE_NONE) {
                 A.outKey[at] = A.ckey[c];

@@ -20,6 +20,7 @@
 #include "hash_dev.h"
 #include "mc_tables.h"
 #include "tsdf.h"
+#include "wave.h"
 
 namespace bf {
 
@@ -188,27 +189,6 @@ __device__ __forceinline__ bool mc_own_empty(const McArgs& A, uint32_t blk) {
     return A.voxels[(size_t)blk * 512 + threadIdx.x].weight == 0.0f;
 }
 
-// exclusive prefix over the workgroup (512 threads = 8 waves); returns the workgroup total in *total
-__device__ __forceinline__ uint32_t wg_exclusive(uint32_t v, uint32_t* sWave, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t n = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += n;
-    }
-    if (lane == 63) sWave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < MC_WG / 64; w++) {
-        const uint32_t s = sWave[w];
-        before += (w < wave) ? s : 0u;
-        all += s;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(MC_WG) void k_mc_count(McArgs A, uint32_t* __restrict__ counts) {
     __shared__ Nbhd nb;
     __shared__ uint32_t sWave[MC_WG / 64];
@@ -227,7 +207,7 @@ __global__ __launch_bounds__(MC_WG) void k_mc_count(McArgs A, uint32_t* __restri
         if (ci >= 0) n = c_mc.ntri[ci];
     }
     uint32_t total;
-    wg_exclusive(n, sWave, &total);
+    wg_exclusive_scan<MC_WG / 64>(n, sWave, total);
     if (threadIdx.x == 0) counts[blk] = total;
 }
 
@@ -237,53 +217,23 @@ __global__ __launch_bounds__(MC_SCAN_CHUNK) void k_mc_scan_chunks(const uint32_t
     __shared__ uint32_t sWave[MC_SCAN_CHUNK / 64];
     const uint32_t i = blockIdx.x * MC_SCAN_CHUNK + threadIdx.x;
     const uint32_t v = i < n ? counts[i] : 0u;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += t;
-    }
-    if (lane == 63) sWave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < MC_SCAN_CHUNK / 64; w++) {
-        const uint32_t s = sWave[w];
-        before += (w < wave) ? s : 0u;
-        all += s;
-    }
-    if (i < n) prefix[i] = before + incl - v;
+    uint32_t all;
+    const uint32_t at = wg_exclusive_scan<MC_SCAN_CHUNK / 64>(v, sWave, all);
+    if (i < n) prefix[i] = at;
     if (threadIdx.x == 0) chunkSum[blockIdx.x] = all;
 }
 
 // exclusive scan of the chunk totals (one workgroup, serial over rounds of 1024); total to out[nChunks]
 __global__ __launch_bounds__(MC_SCAN_CHUNK) void k_mc_scan_top(uint32_t* __restrict__ chunkSum, uint32_t nChunks) {
     __shared__ uint32_t sWave[MC_SCAN_CHUNK / 64];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;  // the same in every lane
     for (uint32_t r = 0; r < nChunks; r += MC_SCAN_CHUNK) {
         const uint32_t i = r + threadIdx.x;
         const uint32_t v = i < nChunks ? chunkSum[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o);
-            if (lane >= (uint32_t)o) incl += t;
-        }
-        if (lane == 63) sWave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < MC_SCAN_CHUNK / 64; w++) {
-            const uint32_t s = sWave[w];
-            before += (w < wave) ? s : 0u;
-            all += s;
-        }
-        const uint32_t c = carry;
-        if (i < nChunks) chunkSum[i] = c + before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry = c + all;
+        uint32_t all;
+        const uint32_t at = carry + wg_exclusive_scan<MC_SCAN_CHUNK / 64>(v, sWave, all);
+        if (i < nChunks) chunkSum[i] = at;
+        carry += all;
         __syncthreads();
     }
     if (threadIdx.x == 0) chunkSum[nChunks] = carry;
@@ -309,7 +259,7 @@ __global__ __launch_bounds__(MC_WG) void k_mc_emit(McArgs A, const uint32_t* __r
     }
     const uint32_t n = ci >= 0 ? c_mc.ntri[ci] : 0u;
     uint32_t total;
-    const uint32_t at = base + wg_exclusive(n, sWave, &total);
+    const uint32_t at = base + wg_exclusive_scan<MC_WG / 64>(n, sWave, total);
     if (n == 0 || at >= cap) return;
     // Voxel v = hashData.getVoxel(worldPos): its colour for every vertex (:178)
     float sdf, w;

@@ -26,6 +26,7 @@
 #include "../../include/bf/bf.h"
 #include "bf_runtime.h"
 #include "sift.h"
+#include "wave.h"
 
 namespace bf {
 
@@ -272,7 +273,6 @@ __global__ __launch_bounds__(256) void k_sift_keys(KeyArgs A) {
     const int r0 = band * (int)Sift::kBandRows, rows = min((int)Sift::kBandRows, h - r0), npix = rows * w;
     const float *g0 = A.g[o][jj], *g1 = A.g[o][jj + 1], *g2 = A.g[o][jj + 2], *g3 = A.g[o][jj + 3];
     uint32_t* stage = A.stage[o * 3 + jj] + (size_t)r0 * w;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t running = 0;
     for (int base = 0; base < npix; base += 256) {
         const int idx = base + (int)threadIdx.x;
@@ -283,16 +283,9 @@ __global__ __launch_bounds__(256) void k_sift_keys(KeyArgs A) {
             col = idx % w;
             flag = key_test(A, o, g0, g1, g2, g3, w, h, row, col);
         }
-        const unsigned long long mask = __ballot(flag);
-        if (lane == 0) waveCnt[wv] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t off = running, total = 0;
-        for (int k = 0; k < 4; k++) {
-            const uint32_t c = waveCnt[k];
-            if (k < wv) off += c;
-            total += c;
-        }
-        if (flag) stage[off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((uint32_t)row << 16) | (uint32_t)col;
+        uint32_t total;
+        const uint32_t off = running + wg_compact_offset<4>(flag, waveCnt, total);
+        if (flag) stage[off] = ((uint32_t)row << 16) | (uint32_t)col;
         running += total;
         __syncthreads();
     }
@@ -496,7 +489,7 @@ __device__ __forceinline__ uint32_t ori_count(uint32_t packed) {
 
 __global__ __launch_bounds__(1024) void k_sift_reshape(ReshapeArgs A) {
     __shared__ uint32_t tot[BF_SIFT_LEVELS], start[BF_SIFT_LEVELS], keep[BF_SIFT_LEVELS], wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < BF_SIFT_LEVELS) tot[tid] = 0;
     __syncthreads();
     for (int L = 0; L < BF_SIFT_LEVELS; L++) {
@@ -549,20 +542,8 @@ __global__ __launch_bounds__(1024) void k_sift_reshape(ReshapeArgs A) {
                 cr = A.rawList[A.listOff[L] + i];
             }
             const uint32_t c = ori_count(packed);
-            uint32_t incl = c;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            if (lane == 63) wsum[wv] = incl;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-            for (int k = 0; k < 16; k++) {
-                const uint32_t t = wsum[k];
-                if (k < wv) before += t;
-                total += t;
-            }
-            const uint32_t p = running + before + incl - c;
+            uint32_t total;
+            const uint32_t p = running + wg_exclusive_scan<16>(c, wsum, total);
             if (c >= 1 && p < kp) A.fin[start[L] + p] = make_uint4(cr, (uint32_t)L, __float_as_uint(factor * (float)(packed & 0xFFFFu)), 0u);
             if (c == 2 && p + 1 < kp) A.fin[start[L] + p + 1] = make_uint4(cr, (uint32_t)L, __float_as_uint(factor * (float)(packed >> 16)), 0u);
             running += total;

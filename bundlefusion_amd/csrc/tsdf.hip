@@ -17,6 +17,7 @@
 #include "tsdf.h"
 #include "../../include/bf/bf.h"
 #include "hash_dev.h"
+#include "wave.h"
 
 #include <hip/hip_ext.h>
 
@@ -81,12 +82,6 @@ __host__ __device__ __forceinline__ BFMat4 op_mat(const float* m) {
     for (int i = 0; i < 12; i++) r.m[i] = m[i];
     r.m[12] = 0.0f; r.m[13] = 0.0f; r.m[14] = 0.0f; r.m[15] = 1.0f;
     return r;
-}
-
-__device__ __forceinline__ unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ unsigned long long lanemask_lt() {
-    unsigned l = lane_id();
-    return l == 0 ? 0ull : (~0ull >> (64 - l));
 }
 
 // 12-B voxel as one 4-byte-aligned unit, so loads/stores become single dwordx3 accesses
@@ -627,7 +622,7 @@ __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&s_nkeys, (uint32_t)__popcll(m));
         base = __shfl(base, 0);
-        if (full) set[base + __popcll(m & lanemask_lt())] = key;
+        if (full) set[base + ballot_rank(m, lane)] = key;
     }
     __syncthreads();
     const uint32_t nkeys = s_nkeys;
@@ -638,7 +633,7 @@ __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __
         const unsigned long long m = __ballot(want);
         if (want) {
             const int leader = __ffsll((long long)m) - 1;
-            const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
+            const uint32_t rank = ballot_rank(m, lane);
             uint32_t base = 0;
             if ((int)lane_id() == leader) base = atomicAdd(&A.ctrl[C_CAND], (uint32_t)__popcll(m));
             base = __shfl(base, leader);
@@ -747,7 +742,7 @@ __global__ __launch_bounds__(256) void k_alloc_insert(HashArgs A, const unsigned
             }
             old = __shfl(old, leader);
             if (need) {
-                const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
+                const uint32_t rank = ballot_rank(m, lane);
                 const bool ok = old < A.numBlocks && rank <= old;
                 int4* e = reinterpret_cast<int4*>(A.hash + hslot);
                 if (ok) {
@@ -865,7 +860,7 @@ __global__ __launch_bounds__(256) void k_compactify(HashArgs A, BFDepthCameraPar
         __syncthreads();
         uint32_t off0 = s_base;
         for (uint32_t k = 0; k < wv; k++) off0 += s_cnt[k];
-        if (inFr) A.visible[off0 + __popcll(m0 & lanemask_lt())] = make_int4(bp.x, bp.y, bp.z, (int)i);
+        if (inFr) A.visible[off0 + ballot_rank(m0, lane)] = make_int4(bp.x, bp.y, bp.z, (int)i);
         scanned += alloc ? 1 : 0;
         vis += inFr ? 1 : 0;
         __syncthreads();  // s_cnt / s_base reuse
@@ -1168,7 +1163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kScanWpc)))
         uint32_t off0 = s_base;
         for (uint32_t k = 0; k < wv; k++) off0 += s_cnt[k];
         const int4 ent = make_int4(bp.x, bp.y, bp.z, (int)i);
-        if (keepVis) A.visible[off0 + __popcll(m0 & lanemask_lt())] = ent;
+        if (keepVis) A.visible[off0 + ballot_rank(m0, lane)] = ent;
         if (inb) {
             const size_t k = (size_t)bin * binCap + s_bbase[bin] + local;
             A.band[k] = ent;

@@ -803,6 +803,13 @@ int bf_sift_synchronize(bf_sift* s);
 int bf_sift_timer_start(bf_sift* s, bf_timer* t);
 int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
 
+/* test entry of the workgroup scan and ballot compaction that the compaction kernels share (csrc/wave.h): ONE workgroup
+ * of wg lanes (256, 512 or 1024, else BF_ERR_ARG) walks d_in[n] in rounds of wg with a carry. flags == 0: d_out[i] =
+ * d_in[0] + ... + d_in[i - 1] (uint32, wrapping), *d_total = the sum of all n. flags != 0: a word counts as 1 if it is
+ * non-zero. All pointers DEVICE; a NULL d_total, or a NULL d_in / d_out with n > 0, is BF_ERR_ARG (checked before any
+ * device call). Synchronizes the device. */
+int bf_debug_wg_scan(const uint32_t* d_in, uint32_t n, uint32_t wg, int flags, uint32_t* d_out, uint32_t* d_total);
+
 /* ---- mesh output: CUDAMarchingCubesHashSDF::saveMesh (CUDAMarchingCubesHashSDF.cpp:48-105) ------
  * Triangle soup (HOST BFMcTriangle[n], e.g. from bf_scene_extract_mesh) -> indexed mesh as saveMesh
  * builds it: mergeCloseVertices(1e-5, approx) (vertices snapped to a 1e-5 grid, first occurrence kept,

@@ -63,6 +63,20 @@ def test_error_path_without_device():
     assert b"null" in bfa.lib().bf_last_error()
 
 
+def test_debug_wg_scan_argument_checks_without_device():
+    """bf_debug_wg_scan refuses null pointers and workgroup sizes other than 256 / 512 / 1024 before any device call."""
+    L = bfa.lib()
+    word = (C.c_uint32 * 4)()  # never dereferenced: every call below is refused
+    p = C.cast(word, C.c_void_p)
+    for d_in, d_out, d_total in ((None, p, p), (p, None, p), (p, p, None), (None, None, None)):
+        assert L.bf_debug_wg_scan(d_in, C.c_uint32(4), C.c_uint32(256), C.c_int(0), d_out, d_total) == -2  # BF_ERR_ARG
+        assert b"null" in L.bf_last_error()
+    assert L.bf_debug_wg_scan(None, C.c_uint32(0), C.c_uint32(256), C.c_int(1), None, None) == -2
+    for wg in (0, 64, 128, 255, 768, 2048):
+        assert L.bf_debug_wg_scan(p, C.c_uint32(4), C.c_uint32(wg), C.c_int(0), p, p) == -2, wg
+        assert b"wg" in L.bf_last_error()
+
+
 def test_synthetic_stream_host():
     scene = bfa.synth_scene(0)
     cam = bfa.depth_camera(80, 60, fx=577.87 / 8, fy=577.87 / 8)
