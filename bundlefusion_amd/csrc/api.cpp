@@ -40,6 +40,7 @@ uint32_t synth_correspondences(const BFSynthScene& sc, const float* poses, uint3
 void synth_cache_frame(const BFSynthScene& sc, const BFMat4& T, const BFDepthCameraParams& cam, float* depth, float* campos,
                        float* normals, uint8_t* normalsU8, float* intensity, float* intensityDeriv);
 void debug_wg_scan(const uint32_t* in, uint32_t n, uint32_t wg, bool flags, uint32_t* out, uint32_t* total);
+void debug_mc_scan(const uint32_t* counts, uint32_t n, uint32_t* prefix, uint32_t* chunkSum);
 
 // General cofactor inverse, cuda_SimpleMatrixUtil.h:980-1090 (host side of setLastRigidTransform,
 // CUDASceneRepHashSDF.h:128-134).
@@ -1492,6 +1493,11 @@ int bf_sift_debug_raw_keys(bf_sift* s, uint32_t levelIndex, int32_t* colRow, uin
 int bf_debug_wg_scan(const uint32_t* d_in, uint32_t n, uint32_t wg, int flags, uint32_t* d_out, uint32_t* d_total) {
     BF_TRY
     debug_wg_scan(d_in, n, wg, flags != 0, d_out, d_total);
+    BF_CATCH
+}
+int bf_debug_mc_scan(const uint32_t* d_counts, uint32_t n, uint32_t* d_prefix, uint32_t* d_chunk) {
+    BF_TRY
+    debug_mc_scan(d_counts, n, d_prefix, d_chunk);
     BF_CATCH
 }
 int bf_sift_synchronize(bf_sift* s) {

@@ -284,7 +284,25 @@ __global__ __launch_bounds__(MC_WG) void k_mc_emit(McArgs A, const uint32_t* __r
     }
 }
 
+// The two-level exclusive scan of n block counts: prefix[i] = the sum of the counts before i within i's chunk of
+// MC_SCAN_CHUNK, chunkSum[c] = the sum of the chunks before c, chunkSum[nChunks] = the sum of all n
+// (chunkSum holds nChunks + 1 words). Count i's offset is chunkSum[i / MC_SCAN_CHUNK] + prefix[i].
+void mc_scan(const uint32_t* counts, uint32_t n, uint32_t* prefix, uint32_t* chunkSum, hipStream_t stream) {
+    const uint32_t nChunks = (n + MC_SCAN_CHUNK - 1) / MC_SCAN_CHUNK;
+    k_mc_scan_chunks<<<nChunks, MC_SCAN_CHUNK, 0, stream>>>(counts, n, prefix, chunkSum);
+    k_mc_scan_top<<<1, MC_SCAN_CHUNK, 0, stream>>>(chunkSum, nChunks);
+    BF_HIP(hipGetLastError());
+}
+
 }  // namespace
+
+// test entry (bf_debug_mc_scan, tests/test_render_edges_gpu.py): the scan alone, at lengths no scene reaches
+void debug_mc_scan(const uint32_t* counts, uint32_t n, uint32_t* prefix, uint32_t* chunkSum) {
+    BF_REQUIRE(counts != nullptr && prefix != nullptr && chunkSum != nullptr, BF_ERR_ARG, "null pointer");
+    BF_REQUIRE(n > 0, BF_ERR_ARG, "n is 0");
+    mc_scan(counts, n, prefix, chunkSum, nullptr);
+    BF_HIP(hipDeviceSynchronize());
+}
 
 uint32_t Scene::extractMesh(const BFMarchingCubesParams& p, BFMcTriangle* out, uint32_t cap, uint32_t* total) {
     BF_REQUIRE(p.threshMarchingCubes > 0.0f && p.threshMarchingCubes2 > 0.0f, BF_ERR_ARG, "marching-cubes thresholds must be > 0");
@@ -317,9 +335,7 @@ uint32_t Scene::extractMesh(const BFMarchingCubesParams& p, BFMcTriangle* out, u
     chunkSum.alloc(nChunks + 1);
     k_mc_count<<<hw, MC_WG, 0, stream_>>>(A, counts.p);
     BF_HIP(hipGetLastError());
-    k_mc_scan_chunks<<<nChunks, MC_SCAN_CHUNK, 0, stream_>>>(counts.p, hw, prefix.p, chunkSum.p);
-    k_mc_scan_top<<<1, MC_SCAN_CHUNK, 0, stream_>>>(chunkSum.p, nChunks);
-    BF_HIP(hipGetLastError());
+    mc_scan(counts.p, hw, prefix.p, chunkSum.p, stream_);
     if (cap > 0) {
         k_mc_emit<<<hw, MC_WG, 0, stream_>>>(A, prefix.p, chunkSum.p, out, cap);
         BF_HIP(hipGetLastError());

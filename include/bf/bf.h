@@ -809,6 +809,12 @@ int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
  * non-zero. All pointers DEVICE; a NULL d_total, or a NULL d_in / d_out with n > 0, is BF_ERR_ARG (checked before any
  * device call). Synchronizes the device. */
 int bf_debug_wg_scan(const uint32_t* d_in, uint32_t n, uint32_t wg, int flags, uint32_t* d_out, uint32_t* d_total);
+/* test entry of mesh extraction's two-level scan (csrc/mc.hip), at lengths no scene reaches: with C = 1024,
+ * d_prefix[i] = the sum of d_counts before i within i's chunk of C, d_chunk[c] = the sum of the chunks before c,
+ * d_chunk[ceil(n / C)] = the sum of all n (uint32, wrapping), so count i's offset is d_chunk[i / C] + d_prefix[i].
+ * All pointers DEVICE; d_prefix holds n words, d_chunk ceil(n / C) + 1. n == 0 or a NULL pointer is BF_ERR_ARG (checked
+ * before any device call). Synchronizes the device. */
+int bf_debug_mc_scan(const uint32_t* d_counts, uint32_t n, uint32_t* d_prefix, uint32_t* d_chunk);
 
 /* ---- mesh output: CUDAMarchingCubesHashSDF::saveMesh (CUDAMarchingCubesHashSDF.cpp:48-105) ------
  * Triangle soup (HOST BFMcTriangle[n], e.g. from bf_scene_extract_mesh) -> indexed mesh as saveMesh

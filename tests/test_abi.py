@@ -77,6 +77,18 @@ def test_debug_wg_scan_argument_checks_without_device():
         assert b"wg" in L.bf_last_error()
 
 
+def test_debug_mc_scan_argument_checks_without_device():
+    """bf_debug_mc_scan refuses a null pointer and n == 0 before any device call."""
+    L = bfa.lib()
+    word = (C.c_uint32 * 4)()  # never dereferenced: every call below is refused
+    p = C.cast(word, C.c_void_p)
+    for d_counts, d_prefix, d_chunk in ((None, p, p), (p, None, p), (p, p, None), (None, None, None)):
+        assert L.bf_debug_mc_scan(d_counts, C.c_uint32(4), d_prefix, d_chunk) == -2  # BF_ERR_ARG
+        assert b"null" in L.bf_last_error()
+    assert L.bf_debug_mc_scan(p, C.c_uint32(0), p, p) == -2
+    assert b"n is 0" in L.bf_last_error()
+
+
 def test_synthetic_stream_host():
     scene = bfa.synth_scene(0)
     cam = bfa.depth_camera(80, 60, fx=577.87 / 8, fy=577.87 / 8)

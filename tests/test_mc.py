@@ -1,13 +1,13 @@
-"""Marching-cubes mesh extraction (CUDAMarchingCubesHashSDF::extractIsoSurface + saveMesh,
-/root/reference/FriedLiver/Source/DepthSensing/CUDAMarchingCubesHashSDF.cpp:48-118,
-MarchingCubesSDFUtil.h:119-227).
+"""Marching-cubes mesh extraction (CUDAMarchingCubesHashSDF::extractIsoSurface + saveMesh, the reference's
+FriedLiver/Source/DepthSensing/CUDAMarchingCubesHashSDF.cpp:48-118, MarchingCubesSDFUtil.h:119-227).
 
 CPU: the compiled case tables against the reference's own Tables.h (golden fixture), an analytic
 known-answer test of the oracle restatement (a fronto-parallel wall: the projective SDF is linear in
 z, so every vertex lies on the wall), and the host mesh merge / PLY writer of the C ABI.
 GPU: bf_scene_extract_mesh against the oracle on identical volumes, bit for bit (as multisets: heap
 block numbering follows the allocation schedule); the GPU's fixed output order run to run; the
-maxNumTriangles cap and the box filter."""
+maxNumTriangles cap and the box filter. tests/test_render_edges_gpu.py adds worlds far from the origin, rejecting
+thresholds, lattice surfaces, boxes through voxel centres, every split of the cap and the scan beyond 1024 chunks."""
 import json
 import os
 import struct

@@ -2,9 +2,10 @@
 against the oracle's restatement of CUDARayCastSDF::render on identical volumes.
 
 Both sides evaluate the same float32 expressions in the same order (-ffp-contract=off), so the
-rendered depth / depth4 / colour / normal bits are expected to be identical; the stated bar
-(>= 99.5 % validity agreement, |d depth| <= 1 mm) is asserted as the fallback
-and the exact-match fraction is required to be >= 99.9 %."""
+rendered depth / depth4 / colour / normal bits are identical at every pixel of every render here
+(measured: exact-match fraction 1.0), and that is what is required; the stated bar
+(>= 99.5 % validity agreement, |d depth| <= 1 mm) is asserted first as the coarser
+check. tests/test_render_edges_gpu.py renders the sizes, poses and worlds these leave out."""
 import numpy as np
 import pytest
 
@@ -26,7 +27,7 @@ def build(W=160, H=120, vs=0.01, frames=(0, 3, 6, 9), noise=1, **scene_opts):
     return sc, cam, pair, f
 
 
-def compare(g, o, min_exact=0.999):
+def compare(g, o, min_exact=1.0):
     gd, g4, gn, gc = g[:4]
     od, o4, on, oc = o[:4]
     gv, ov = np.isfinite(gd), np.isfinite(od)
@@ -36,10 +37,12 @@ def compare(g, o, min_exact=0.999):
     assert both.sum() > 0
     assert np.max(np.abs(gd[both] - od[both])) <= 1e-3
     exact = np.mean((gd.view(np.uint32) == od.view(np.uint32)))
+    print(f"exact-match fraction: depth {exact:.6f} of {gd.size} pixels")
     assert exact >= min_exact, exact
-    for a, b in ((g4, o4), (gc, oc), (gn, on)):
+    for name, a, b in (("depth4", g4, o4), ("colour", gc, oc), ("normals", gn, on)):
         same = np.all(a.view(np.uint32) == b.view(np.uint32), axis=-1)
-        assert np.mean(same) >= min_exact
+        print(f"exact-match fraction: {name} {np.mean(same):.6f}")
+        assert np.mean(same) >= min_exact, (name, np.mean(same))
     return gv.mean()
 
 
