@@ -23,39 +23,46 @@ MODES = [bfa.abi.NORMAL_EQ_MATRIX_FREE, bfa.abi.NORMAL_EQ_ASSEMBLED]
 
 
 def gpu_solve(prob, n_nonlin, n_lin, ws, wd=None, wc=None, use_cache=False, max_corr=None, corr=None, mode=None,
-              shard=None, export=False, early_out=True, pcg_launch=0, pcg_spin_limit_us=0):
+              shard=None, export=False, early_out=True, pcg_launch=0, pcg_spin_limit_us=0, max_images=None, valid=None,
+              handle=None, rebuild_jt=True):
     """mode: normal equations (None = auto: assembled for sparse-only solves); shard = (count, index);
-    pcg_launch: 0 auto (one persistent PCG launch per GN step where it fits), 1 one launch per iteration."""
+    pcg_launch: 0 auto (one persistent PCG launch per GN step where it fits), 1 one launch per iteration;
+    max_images: the handle's capacity (default: the problem's image count); valid: the image flags instead of the
+    problem's; handle: a SolverBundling to solve on, which is left open (its options are its own: mode, early_out,
+    pcg_launch, pcg_spin_limit_us, max_images and max_corr are not looked at); rebuild_jt=False keeps the handle's
+    row and pair tables of its previous solve."""
     from bundlefusion_amd.solver import DeviceCache, SolverBundling
     K = prob["K"]
     corr = prob["corr"] if corr is None else corr
-    max_corr = max_corr or max(K * 4000, len(corr))
-    S = SolverBundling(K, max_corr, normal_equations=mode, early_out=early_out, pcg_launch=pcg_launch,
-                       pcg_spin_limit_us=pcg_spin_limit_us)
+    max_corr = max_corr or max((max_images or K) * 4000, len(corr))
+    S = handle or SolverBundling(max_images or K, max_corr, normal_equations=mode, early_out=early_out,
+                                 pcg_launch=pcg_launch, pcg_spin_limit_us=pcg_spin_limit_us)
     if shard is not None:
         S.set_shard(*shard)
     d_corr = bfa.DeviceArray.from_host(corr if len(corr) else np.zeros(1, corr.dtype))
-    d_valid = bfa.DeviceArray.from_host(prob["valid"].astype(np.int32))
+    d_valid = bfa.DeviceArray.from_host((prob["valid"] if valid is None else valid).astype(np.int32))
     d_rot = bfa.DeviceArray.from_host(prob["rot"].astype(np.float32))
     d_trans = bfa.DeviceArray.from_host(prob["trans"].astype(np.float32))
     cache = DeviceCache(prob["cache"]) if use_cache else None
     S.solve(d_corr, len(corr), d_valid, K, n_nonlin, n_lin, ws, wd, wc,
             cache=cache.table if cache else None, cache_w=cache.W if cache else 0, cache_h=cache.H if cache else 0,
-            intrinsics=prob.get("intrinsics", (0, 0, 0, 0)), rot=d_rot, trans=d_trans)
+            intrinsics=prob.get("intrinsics", (0, 0, 0, 0)), rot=d_rot, trans=d_trans, rebuild_jt=rebuild_jt)
     res = S.result()
     out = d_rot.download(), d_trans.download(), d_corr.download()[:len(corr)], res
     if export:
         out = out + (S.export_pairs(),)
-    S.close()
+    if handle is None:
+        S.close()
     return out
 
 
 def oracle_solve(prob, n_nonlin, n_lin, ws, wd=None, wc=None, use_cache=False, max_corr=None, corr=None,
-                 early_out=True):
+                 early_out=True, valid=None):
     K = prob["K"]
     corr = prob["corr"] if corr is None else corr
     max_corr = max_corr or max(K * 4000, len(corr))
-    return solve(corr, prob["valid"], prob["rot"], prob["trans"], n_nonlin, n_lin, ws, wd, wc,
+    valid = prob["valid"] if valid is None else valid
+    return solve(corr, valid, prob["rot"], prob["trans"], n_nonlin, n_lin, ws, wd, wc,
                  cache=prob.get("cache") if use_cache else None, intrinsics=prob.get("intrinsics", (0, 0, 0, 0)),
                  max_corr_per_img=max_corr_per_image(K, max_corr), early_out=early_out)
 
@@ -497,8 +504,10 @@ def test_persistent_pcg_timeout_is_redone(case):
 
 @pytest.mark.parametrize("mode", MODES)
 def test_many_images_multipass_finisher(mode):
-    """More than 2 x 256 images: the PCG finisher takes its multi-pass path (rows do not fit the
-    register-resident form); one GN step with a few PCG iterations tracks the oracle tightly."""
+    """More than 2 x 256 + 1 images. In the matrix-free mode k_pcg's finisher holds 2 image rows per thread in
+    registers up to 513 images and takes its multi-pass form here. In the assembled mode 560 images run
+    k_pcg_pairs<8>, whose finisher keeps 8 rows per thread in registers up to 2 049 images: its multi-pass form
+    is reached at 2 050 (test_ba_edges_gpu.py). One GN step with a few PCG iterations tracks the oracle tightly."""
     prob = make_problem(K=560, stride=1, max_per_pair=4, outliers=0.0, drift=(0.05, 0.002))
     g, o = gpu_solve(prob, 1, 5, [1], mode=mode), oracle_solve(prob, 1, 5, [1])
     assert g[3]["pcgIterations"] == o[3]["pcgIterations"] == 5
