@@ -383,4 +383,7 @@ def __getattr__(name):  # the matcher and detector bindings import this module's
     if name in ("Sift", "sift_options"):
         from . import sift
         return getattr(sift, name)
+    if name in ("Bundler", "bundler_options"):
+        from . import bundler
+        return getattr(bundler, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -242,12 +242,44 @@ class BFSiftOptions(C.Structure):  # include/bf/types.h: the SIFT detector (bf_s
                 ("edgeThreshold", C.c_float), ("reserved", C.c_uint32)]
 
 
+class BFBundlerOptions(C.Structure):  # include/bf/types.h: the bundler (bf_bundler_*)
+    _fields_ = [("sift", BFSiftOptions), ("local", BFMatcherOptions), ("global_", BFMatcherOptions),
+                ("verify", BFMatchVerifyOptions), ("cache", BFCacheOptions), ("submapSize", C.c_uint32),
+                ("maxKeyframes", C.c_uint32), ("maxLocalCorr", C.c_uint32), ("maxGlobalCorr", C.c_uint32),
+                ("colorIntrinsics", C.c_float * 16), ("filterIntensity", C.c_uint32), ("intensitySigmaD", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class BFBundlerFrame(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("frame", "localFrame", "submap", "numKeys", "siftFlags", "valid", "lastMatchedLocal",
+                                          "residualsAdded", "residualsTotal", "submapClosed")] + [
+        ("siftPose", C.c_float * 16), ("integrateTransform", C.c_float * 16)]
+
+
+class BFBundlerSubmap(C.Structure):
+    _fields_ = [("d_corr", C.c_void_p), ("d_keyIdx", C.c_void_p), ("d_validImages", C.c_void_p),
+                ("validImages", C.POINTER(C.c_int32)), ("cacheFrames", C.POINTER(BFCachedFrame)),
+                ("d_cacheFrames", C.c_void_p)] + [
+        (n, C.c_uint32) for n in ("numCorr", "numFrames", "submap", "isValid", "released", "reserved")]
+
+
+class BFBundlerKeyframe(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("keyframe", "numKeys", "numTracks", "valid", "lastMatchedGlobal", "residualsAdded",
+                                          "residualsTotal", "globalTrackingLost")]
+
+
+class BFBundlerStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "hostWaits", "keyframes")]
+
+
+BUNDLER_NO_FRAME, BUNDLER_LOCAL, BUNDLER_OPT_LOCAL, BUNDLER_GLOBAL = 0xFFFFFFFF, 0, 1, 2
 SIFT_LEVELS, SIFT_MAX_FILTER, SIFT_TRUNCATED = 12, 33, 1
 SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
 MAX_MATCHES_RAW, MAX_MATCHES_FILTERED, MATCH_MAX_KEYS_PER_IMAGE = 128, 25, 1024
 assert C.sizeof(BFSiftKeyPoint) == 16 and SIFT_KEYPOINT_DTYPE.itemsize == 16
 assert C.sizeof(BFMatchVerifyOptions) == 32
 assert C.sizeof(BFSiftOptions) == 48
+assert C.sizeof(BFBundlerFrame) == 168
 
 
 class BFVoxelOp(C.Structure):  # include/bf/bf.h

@@ -16,6 +16,7 @@
 #include "frontend.h"
 #include "match.h"
 #include "sift.h"
+#include "bundler.h"
 
 #include <cstring>
 #include <memory>
@@ -152,6 +153,14 @@ struct bf_sift {
     Sift* s = nullptr;
 };
 
+// the stage handles inside are BORROWED views of the bundler's own objects and stream: never destroyed on their own
+struct bf_bundler {
+    Bundler* b = nullptr;
+    bf_sift sift;
+    bf_matcher matcher[3];
+    bf_cache cache[3];
+};
+
 extern "C" {
 
 int bf_abi_version(void) { return BF_ABI_VERSION; }
@@ -197,7 +206,12 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFAppTiming", sizeof(BFAppTiming)},
         {"BFMcTriangle", sizeof(BFMcTriangle)},
         {"BFSynthScene", sizeof(BFSynthScene)},
-        {"BFRenderStats", sizeof(BFRenderStats)}};
+        {"BFRenderStats", sizeof(BFRenderStats)},
+        {"BFBundlerOptions", sizeof(BFBundlerOptions)},
+        {"BFBundlerFrame", sizeof(BFBundlerFrame)},
+        {"BFBundlerSubmap", sizeof(BFBundlerSubmap)},
+        {"BFBundlerKeyframe", sizeof(BFBundlerKeyframe)},
+        {"BFBundlerStats", sizeof(BFBundlerStats)}};
     for (const auto& e : kSizes)
         if (std::strcmp(e.n, name) == 0) {
             *out = e.s;
@@ -1518,6 +1532,144 @@ int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms) {
     BF_HIP(hipEventRecord(t->b, s->stream));
     BF_HIP(hipEventSynchronize(t->b));
     BF_HIP(hipEventElapsedTime(ms, t->a, t->b));
+    BF_CATCH
+}
+
+// ---- bundler (Bundler x 3 + the input half of OnlineBundler) ----------------------------------------
+static void bundler_refresh(bf_bundler* h) {  // the borrowed handles follow the local sets' swap
+    h->sift.stream = h->b->stream();
+    h->sift.s = &h->b->sift();
+    for (uint32_t w = 0; w < 3; w++) {
+        h->matcher[w].stream = h->cache[w].stream = h->b->stream();
+        h->matcher[w].m = &h->b->matcher(w);
+        h->cache[w].c = &h->b->cache(w);
+    }
+}
+int bf_bundler_create(const BFBundlerOptions* opts, bf_bundler** out) {
+    BF_TRY
+    BF_REQUIRE(opts && out, BF_ERR_ARG, "null argument");
+    *out = nullptr;
+    const BundlerConfig cfg = make_bundler_config(opts);  // every option check before any device work
+    std::unique_ptr<bf_bundler> h(new bf_bundler());
+    h->b = new Bundler(cfg);
+    bundler_refresh(h.get());
+    *out = h.release();
+    BF_CATCH
+}
+int bf_bundler_destroy(bf_bundler* b) {
+    BF_TRY
+    if (b) {
+        delete b->b;
+        delete b;
+    }
+    BF_CATCH
+}
+int bf_bundler_reset(bf_bundler* b) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->reset();
+    bundler_refresh(b);
+    BF_CATCH
+}
+int bf_bundler_synchronize(bf_bundler* b) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    BF_HIP(hipStreamSynchronize(b->b->stream()));
+    BF_CATCH
+}
+int bf_bundler_timer_start(bf_bundler* b, bf_timer* t) {
+    BF_TRY
+    BF_REQUIRE(b && t, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->a, b->b->stream()));
+    BF_CATCH
+}
+int bf_bundler_timer_stop(bf_bundler* b, bf_timer* t, float* ms) {
+    BF_TRY
+    BF_REQUIRE(b && t && ms, BF_ERR_ARG, "null argument");
+    BF_HIP(hipEventRecord(t->b, b->b->stream()));
+    BF_HIP(hipEventSynchronize(t->b));
+    BF_HIP(hipEventElapsedTime(ms, t->a, t->b));
+    BF_CATCH
+}
+int bf_bundler_process_frame(bf_bundler* b, const uint8_t* d_color, uint32_t colorW, uint32_t colorH, const float* d_depthFilt,
+                             const float* d_depthRaw, BFBundlerFrame* out) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    struct Refresh {  // also when the frame ends in BF_ERR_CAPACITY: the swap has happened by then
+        bf_bundler* h;
+        ~Refresh() { bundler_refresh(h); }
+    } refresh{b};
+    b->b->processFrame(d_color, colorW, colorH, d_depthFilt, d_depthRaw, out);
+    BF_CATCH
+}
+int bf_bundler_set_complete_trajectory(bf_bundler* b, const float* d_T, uint32_t n, uint32_t lastValidCompleteTransform) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->setCompleteTrajectory(d_T, n, lastValidCompleteTransform);
+    BF_CATCH
+}
+int bf_bundler_submap(bf_bundler* b, BFBundlerSubmap* out) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->submap(out);
+    BF_CATCH
+}
+int bf_bundler_fuse_submap(bf_bundler* b, const float* d_localTransforms, BFBundlerKeyframe* out) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->fuseSubmap(d_localTransforms, out);
+    BF_CATCH
+}
+int bf_bundler_invalid_submap(bf_bundler* b) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->invalidSubmap();
+    BF_CATCH
+}
+int bf_bundler_global(bf_bundler* b, BFEntryJ** d_corr, const uint32_t** d_keyIdx, uint32_t* n, const uint32_t** prefix,
+                      uint32_t* numKeyframes) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->global(d_corr, d_keyIdx, n, prefix, numKeyframes);
+    BF_CATCH
+}
+int bf_bundler_matcher(bf_bundler* b, uint32_t which, bf_matcher** out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    BF_REQUIRE(which <= BF_BUNDLER_GLOBAL, BF_ERR_ARG, "which is BF_BUNDLER_LOCAL, _OPT_LOCAL or _GLOBAL");
+    *out = &b->matcher[which];
+    BF_CATCH
+}
+int bf_bundler_cache(bf_bundler* b, uint32_t which, bf_cache** out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    BF_REQUIRE(which <= BF_BUNDLER_GLOBAL, BF_ERR_ARG, "which is BF_BUNDLER_LOCAL, _OPT_LOCAL or _GLOBAL");
+    *out = &b->cache[which];
+    BF_CATCH
+}
+int bf_bundler_sift(bf_bundler* b, bf_sift** out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    *out = &b->sift;
+    BF_CATCH
+}
+int bf_bundler_intensity(bf_bundler* b, const float** d_intensity) {
+    BF_TRY
+    BF_REQUIRE(b && d_intensity, BF_ERR_ARG, "null argument");
+    BF_REQUIRE(b->b->intensity() != nullptr, BF_ERR_STATE, "bf_bundler_intensity before a frame");
+    *d_intensity = b->b->intensity();
+    BF_CATCH
+}
+int bf_bundler_stats(bf_bundler* b, BFBundlerStats* out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    *out = b->b->stats();
+    BF_CATCH
+}
+int bf_bundler_debug_reclose(bf_bundler* b, BFBundlerFrame* out) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->debugReclose(out);
     BF_CATCH
 }
 

@@ -20,6 +20,9 @@ struct CacheConfig {
     float depthSigmaD, depthSigmaR;     // s_depthDownSigmaD [1.0], s_depthDownSigmaR [0.05]
 };
 
+// every check the ctor and storeFrame make on a configuration; throws BF_ERR_ARG (host only, before any device work)
+void check_cache_config(const CacheConfig& cfg);
+
 class Cache {
 public:
     Cache(const CacheConfig& cfg, hipStream_t stream);
@@ -29,6 +32,7 @@ public:
     // copyCacheFrameFrom (CUDACache.h:24-39) / incrementCache (:41-43)
     uint32_t copyFrameFrom(const Cache& other, uint32_t frame);
     void increment();
+    void reset() { cur_ = 0; }  // CUDACache::reset: the next frame stored is frame 0 again
     BFCachedFrame frame(uint32_t i) const;
     uint32_t numFrames() const { return cur_; }
     const CacheConfig& config() const { return cfg_; }

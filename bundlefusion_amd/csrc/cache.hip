@@ -225,11 +225,17 @@ __global__ __launch_bounds__(256) void k_cache_intensity(IntArgs A) {
 
 BFMat4 mat4_inverse(const BFMat4& m);  // api.cpp
 
-Cache::Cache(const CacheConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(stream) {
+void check_cache_config(const CacheConfig& cfg) {
     BF_REQUIRE(cfg.inputWidth >= 2 && cfg.inputHeight >= 2 && cfg.width >= 2 && cfg.height >= 2, BF_ERR_ARG,
                "cache and input sizes must be >= 2");
     BF_REQUIRE((size_t)cfg.width * cfg.height <= MAX_CACHE_PIXELS, BF_ERR_ARG, "cache size above 2^20 pixels");
     BF_REQUIRE(cfg.maxFrames > 0, BF_ERR_ARG, "maxFrames");
+    if (cfg.depthSigmaD > 0.0f) (void)gauss_table(cfg.depthSigmaD);  // radius <= 7
+    if (cfg.colorSigma > 0.0f) (void)gauss_table(cfg.colorSigma);
+}
+
+Cache::Cache(const CacheConfig& cfg, hipStream_t stream) : cfg_(cfg), stream_(stream) {
+    check_cache_config(cfg);
     hw_ = (size_t)cfg.width * cfg.height;
     // CUDACache::CUDACache (CUDACache.cpp:15-42): intrinsics scaled to the cache size
     std::memcpy(K_, cfg.inputIntrinsics, 64);

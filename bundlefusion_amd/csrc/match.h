@@ -77,6 +77,28 @@ public:
     void fuseTracks(uint32_t* root, uint32_t* rank, uint8_t* good);
     void imageKeys(uint32_t image, BFSiftKeyPoint* keys, uint8_t* descs);
 
+    // ---- what the bundler's closing launch (bundler.hip, k_frame_close) needs; none of it changes a member above ----
+    // device views of the state filterFrames / addToResiduals / transforms read on the host
+    struct CloseView {
+        const BFSiftKeyPoint* keys;
+        const uint32_t* filtCount;
+        const uint2* filtIdx;
+        const uint32_t* table;  // per image {offset, count, valid, 0}
+        const float* Tinv;
+        const float* kinv;      // intrinsicsInv, 16 floats
+        uint32_t* base;         // [maxImages] EntryJ base per pair, the array k_add_residuals reads
+    };
+    // the argument checks of filterFrames, the image table brought up to date on the device, then the views
+    CloseView prepareClose(uint32_t cur, uint32_t start);
+    // filterFrames' host half once the closing launch has decided: valid_[cur] from its record
+    void applyClose(uint32_t cur, bool valid) { setValid(cur, valid); }
+    // The caller has just waited for this matcher's stream: no earlier table upload can still read the pinned table,
+    // so the next upload skips its own wait. Without this call every upload waits, as before.
+    void streamDrained() { tableInFlight_ = false; }
+    // Bundler::copyFrame's sparse half: image `image` of src becomes this store's next image (device-to-device)
+    uint32_t copyImageFrom(const Matcher& src, uint32_t image);
+    hipStream_t stream() const { return stream_; }
+
 private:
     uint32_t appendStored(uint32_t n);  // the bookkeeping of addImage for n keys already in place behind the last image
     void uploadTable();
@@ -88,6 +110,7 @@ private:
     std::vector<int> valid_;
     uint32_t totalKeys_ = 0;
     bool tableDirty_ = true;
+    bool tableInFlight_ = true;  // an upload may still read hostTable_ (cleared only by streamDrained)
     DevBuf<BFSiftKeyPoint> keys_;  // [maxImages * maxKeys], linear
     DevBuf<uint8_t> descs_;        // [maxImages * maxKeys][128]
     DevBuf<int32_t> sums_;         // byte sum per descriptor

@@ -39,6 +39,7 @@
 #include "bf_math.h"
 #include "bf_runtime.h"
 #include "match.h"
+#include "match_dev.h"
 #include "wave.h"
 
 namespace bf {
@@ -340,17 +341,7 @@ struct FilterArgs {
     float maxRes2;
 };
 
-// float4x4 * float3 with w = 1 (cuda_SimpleMatrixUtil.h:937-945)
-__device__ __forceinline__ void xform3(const float* e, float x, float y, float z, float* o) {
-    o[0] = e[0] * x + e[1] * y + e[2] * z + e[3] * 1.0f;
-    o[1] = e[4] * x + e[5] * y + e[6] * z + e[7] * 1.0f;
-    o[2] = e[8] * x + e[9] * y + e[10] * z + e[11] * 1.0f;
-}
-
-// camera-space point of a key: intrinsicsInv * (depth * (x, y, 1))
-__device__ __forceinline__ void key_point(const float* kinv, const BFSiftKeyPoint& k, float* o) {
-    xform3(kinv, k.depth * k.x, k.depth * k.y, k.depth * 1.0f, o);
-}
+// xform3 / key_point (a key's camera-space point): match_dev.h
 
 // cyclic Jacobi on a symmetric 3x3: a -> diagonal (eigenvalues), V's columns the eigenvectors
 __device__ void jacobi3(double a[3][3], double V[3][3]) {
@@ -1111,7 +1102,8 @@ void Matcher::setValid(uint32_t i, int v) {
 
 void Matcher::uploadTable() {
     if (!tableDirty_) return;
-    BF_HIP(hipStreamSynchronize(stream_));  // an earlier upload may still read the pinned table
+    if (tableInFlight_) BF_HIP(hipStreamSynchronize(stream_));  // an earlier upload may still read the pinned table
+    tableInFlight_ = true;
     const uint32_t n = numImages();
     for (uint32_t i = 0; i < n; i++) {
         hostTable_[4 * i] = off_[i];
@@ -1220,6 +1212,19 @@ uint32_t Matcher::addToResiduals(uint32_t cur, uint32_t start, BFEntryJ* out, ui
         BF_HIP(hipStreamSynchronize(stream_));
     }
     return sum < cap ? sum : cap;
+}
+
+Matcher::CloseView Matcher::prepareClose(uint32_t cur, uint32_t start) {
+    checkFrames(cur, start);
+    uploadTable();
+    return CloseView{keys_.p, filtCount_.p, filtIdx_.p, table_.p, Tinv_.p, (const float*)(base_.p + cfg_.maxImages), base_.p};
+}
+
+uint32_t Matcher::copyImageFrom(const Matcher& src, uint32_t image) {
+    BF_REQUIRE(&src != this, BF_ERR_ARG, "copyImageFrom: source and destination are the same matcher");
+    BF_REQUIRE(image < src.numImages(), BF_ERR_ARG, "copyImageFrom: image >= the source's numImages");
+    const size_t at = src.off_[image];
+    return addImage(src.keys_.p + at, src.descs_.p + at * 128, src.num_[image]);
 }
 
 MatchVerifyConfig make_match_verify_config(const BFMatchVerifyOptions* o) {

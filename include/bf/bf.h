@@ -33,7 +33,9 @@ extern "C" {
                              additive, still 4: its surface-area and dense-verify filters (BFMatchVerifyOptions, bf_match_*);
                              additive, still 4: the SIFT detector (BFSiftOptions, bf_sift_*);
                              additive, still 4: key fusing (BFMatcherOptions.fuseMaxCorr in place of reserved[0],
-                             bf_match_fuse_to_global, bf_match_fuse_tracks, bf_match_image_keys) */
+                             bf_match_fuse_to_global, bf_match_fuse_tracks, bf_match_image_keys);
+                             additive, still 4: the bundler (BFBundlerOptions, BFBundlerFrame, BFBundlerSubmap,
+                             BFBundlerKeyframe, BFBundlerStats, bf_bundler_*) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -802,6 +804,88 @@ int bf_sift_debug_raw_keys(bf_sift* s, uint32_t levelIndex, int32_t* colRow, uin
 int bf_sift_synchronize(bf_sift* s);
 int bf_sift_timer_start(bf_sift* s, bf_timer* t);
 int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
+
+/* ---- bundler: Bundler (Bundler.cpp:91-394) as the local and the global bundler, and the input half of OnlineBundler
+ * (getCurrentFrame, processInput up to prepareLocalSolve, processGlobal without the solves: OnlineBundler.cpp:106-227,
+ * 280-361). One handle owns one detector, two local matchers of submapSize + 1 images (m_local / m_optLocal), one global
+ * matcher of maxKeyframes images, a cache per matcher, the device EntryJ + key-index lists of each, and the device
+ * siftTrajectory / currIntegrateTransform arrays. Everything runs on ONE stream of the handle's own; all device memory is
+ * allocated in bf_bundler_create. The solves stay in bf_solver_* / bf_recon_*: what the bundler emits is what they take.
+ *
+ * A frame ends in one closing launch (csrc/bundler.hip, k_frame_close) that does filterFrames, the exclusive scan of
+ * the filtered counts, AddCurrToResidualsCU at the device-resident end of the list and getSiftTransformCU_Kernel
+ * (OnlineBundler.cu:6-53), and writes one record into pinned host memory. HOST WAIT BUDGETS, counted in BFBundlerStats:
+ *   bf_bundler_process_frame  <= 2: the detector's key count (the store's host table needs it, as
+ *                                   finalizeSIFTImageGPU does), and the record (none for frame 0);
+ *   bf_bundler_fuse_submap    <= 2: the fuse's count read-back, and the record (none for the first key frame);
+ *   bf_bundler_invalid_submap    0.
+ * Out of scope, as DESIGN.md §7 lists: tryRevalidation, the retry list, the global-only trajectory re-initialisation
+ * (Bundler.cpp:223-237). DESIGN.md §3.7 has the semantics and the departures. */
+typedef struct bf_bundler bf_bundler;
+/* OnlineBundler::OnlineBundler (OnlineBundler.cpp:31-91) + Bundler::Bundler x 3 (Bundler.cpp:19-54). Host checks first,
+ * each BF_ERR_ARG and before any device work: null argument; submapSize 0; maxKeyframes < 2; submapSize * maxKeyframes or a
+ * list capacity above 2^28; a field the bundler decides set to another value (BFBundlerOptions); whatever
+ * bf_sift_create, bf_matcher_create, bf_cache_create and the verify options reject; the cache's input size differing
+ * from the detector's depth size; non-finite colorIntrinsics; filterIntensity with a sigma that is not finite, not
+ * positive or above 3.5. */
+int bf_bundler_create(const BFBundlerOptions* opts, bf_bundler** out);
+int bf_bundler_destroy(bf_bundler* b);
+/* Back to the state after create (Bundler::reset x 3, Bundler.cpp:354-360; frame counter, lists, trajectories, stats). */
+int bf_bundler_reset(bf_bundler* b);
+int bf_bundler_synchronize(bf_bundler* b);
+int bf_bundler_timer_start(bf_bundler* b, bf_timer* t);
+int bf_bundler_timer_stop(bf_bundler* b, bf_timer* t, float* ms); /* synchronizes */
+/* OnlineBundler::getCurrentFrame + processInput (OnlineBundler.cpp:106-116, 167-227) for the next frame f: intensity
+ * (resampleToIntensity, then k_gauss_intensity when filterIntensity), detectFeatures into the current local store,
+ * storeCachedFrame; for local frame > 0 matchAndFilter against the submap's earlier frames (match, Kabsch, surface area,
+ * dense verify on the local cache) and the closing launch; when f > 0 and f % submapSize == 0, copyFrame
+ * (Bundler.cpp:284-293) of f into the other local set as its frame 0, then the swap (prepareLocalSolve :161-164).
+ * d_color DEVICE RGBX [colorH][colorW], d_depthFilt / d_depthRaw DEVICE float at the detector's depth size (the
+ * detector reads the filtered, the cache the raw image); all three are read on the bundler's stream: keep them until the
+ * call returns for a frame > 0, until bf_bundler_synchronize for frame 0. *out (HOST, required) is filled.
+ * BF_SIFT_TRUNCATED is no error (out->siftFlags). BF_ERR_ARG: a null argument. BF_ERR_CAPACITY before any device work:
+ * submapSize * maxKeyframes frames have been processed. BF_ERR_STATE before any device work: f closes a submap and the
+ * previous closed submap has not been taken by bf_bundler_fuse_submap / _invalid_submap. BF_ERR_CAPACITY after the
+ * frame: its residuals would pass maxLocalCorr; then nothing was appended, the list and its count are as before, the
+ * frame is stored as an INVALID image (siftPose copied, integrateTransform -inf, *out filled) and the handle goes on. */
+int bf_bundler_process_frame(bf_bundler* b, const uint8_t* d_color, uint32_t colorW, uint32_t colorH, const float* d_depthFilt,
+                             const float* d_depthRaw, BFBundlerFrame* out);
+/* The two inputs of computeSiftTransformCU that the global solve produces (OnlineBundler.cpp:126-129): d_T DEVICE
+ * float[n][16] is copied (stream-ordered) into the handle's completeTrajectory; n <= submapSize * maxKeyframes and
+ * lastValidCompleteTransform < max(n, 1), else BF_ERR_ARG. After create / reset: lastValidCompleteTransform = 0. */
+int bf_bundler_set_complete_trajectory(bf_bundler* b, const float* d_T, uint32_t n, uint32_t lastValidCompleteTransform);
+/* The last closed submap (Bundler::isValid, getValidImages, the EntryJ list, the cache table). Its pointers stay valid
+ * and its contents unchanged until the next submap closes. BF_ERR_STATE: no submap has closed. */
+int bf_bundler_submap(bf_bundler* b, BFBundlerSubmap* out);
+/* OnlineBundler::processGlobal, state PROCESS (OnlineBundler.cpp:302-348): fuseToGlobal of the closed submap with the
+ * solved d_localTransforms (DEVICE float[numFrames][16], frame -> the submap's first frame) = bf_match_fuse_to_global +
+ * the cache copy of frame 0 (Bundler.cpp:388-394); with two or more key frames the global matchAndFilter and the global
+ * closing launch; then the closed local set is reset (:324). *out (HOST, required) is filled. BF_ERR_STATE: no closed
+ * submap waits. What bf_match_fuse_to_global rejects is rejected here; BF_ERR_CAPACITY: the residuals would pass
+ * maxGlobalCorr (nothing appended, the key frame stays stored as invalid). */
+int bf_bundler_fuse_submap(bf_bundler* b, const float* d_localTransforms, BFBundlerKeyframe* out);
+/* ... state INVALIDATE (OnlineBundler.cpp:351-360): Bundler::addInvalidFrame (Bundler.cpp:362-368: an image without keys,
+ * bf_cache_increment) and the reset of the closed local set. BF_ERR_STATE: no closed submap waits. */
+int bf_bundler_invalid_submap(bf_bundler* b);
+/* The global list in the form bf_recon_set_global_correspondences takes: DEVICE EntryJ[*n], HOST prefix[*numKeyframes]
+ * (prefix[k] = entries with max(i, j) <= k). A key frame k is only paired with prev < k, so the list is ordered by
+ * max(i, j) by construction. Any output may be NULL. Valid until the next bf_bundler_fuse_submap / _invalid_submap. */
+int bf_bundler_global(bf_bundler* b, BFEntryJ** d_corr, const uint32_t** d_keyIdx, uint32_t* n, const uint32_t** prefix,
+                      uint32_t* numKeyframes);
+/* BORROWED handles of the stages, for the read-backs that exist (bf_matcher_filtered_matches, bf_match_image_keys,
+ * bf_cache_frame, ...): which = BF_BUNDLER_LOCAL, _OPT_LOCAL or _GLOBAL (else BF_ERR_ARG). They follow the swap: ask again
+ * after a frame that closed a submap. A caller must not add images to them, reset or destroy them, or run a detect on the
+ * detector; bf_match_debug_set_filtered is for tests of the closing launch. They die with the bundler. */
+int bf_bundler_matcher(bf_bundler* b, uint32_t which, bf_matcher** out);
+int bf_bundler_cache(bf_bundler* b, uint32_t which, bf_cache** out);
+int bf_bundler_sift(bf_bundler* b, bf_sift** out);
+/* DEVICE float[height][width]: the intensity image the last frame's detect read (filtered when filterIntensity). */
+int bf_bundler_intensity(bf_bundler* b, const float** d_intensity);
+int bf_bundler_stats(bf_bundler* b, BFBundlerStats* out);
+/* test entry of the closing launch: takes the last frame's residuals off its list again and repeats the launch for it
+ * (after bf_match_debug_set_filtered on the borrowed local matcher). Only right after a bf_bundler_process_frame of a
+ * local frame > 0 that did not close a submap, else BF_ERR_STATE. */
+int bf_bundler_debug_reclose(bf_bundler* b, BFBundlerFrame* out);
 
 /* test entry of the workgroup scan and ballot compaction that the compaction kernels share (csrc/wave.h): ONE workgroup
  * of wg lanes (256, 512 or 1024, else BF_ERR_ARG) walks d_in[n] in rounds of wg with a carry. flags == 0: d_out[i] =

@@ -340,10 +340,77 @@ typedef struct BFSiftOptions {
 #define BF_SIFT_MAX_FILTER 33  /* KERNEL_MAX_WIDTH (ProgramCU.cu:54) */
 #define BF_SIFT_TRUNCATED 1u   /* bf_sift_result flag: more than maxKeys keys were found, the finest were dropped */
 
+/* The bundler (bf_bundler_*): Bundler in its local and global role plus the input half of OnlineBundler. The five option
+ * structs are the stages' own, unchanged; a field the bundler decides itself must be 0 or the value it would take:
+ * local.maxImages (submapSize + 1), global.maxImages (maxKeyframes), local.fuseMaxCorr (maxLocalCorr), cache.maxFrames.
+ * zParametersBundlingDefault.txt values in brackets. */
+typedef struct BFBundlerOptions {
+    BFSiftOptions sift;
+    BFMatcherOptions local;        /* s_siftMatchRatioMaxLocal, s_minNumMatchesLocal */
+    BFMatcherOptions global;       /* s_siftMatchRatioMaxGlobal, s_minNumMatchesGlobal */
+    BFMatchVerifyOptions verify;
+    BFCacheOptions cache;
+    uint32_t submapSize;           /* s_submapSize [10], >= 1 */
+    uint32_t maxKeyframes;         /* s_maxNumImages [1200], >= 2: the global store; submapSize * maxKeyframes frames in all */
+    uint32_t maxLocalCorr;         /* EntryJ capacity of a submap; 0 = 25 * (submapSize + 1) * submapSize / 2 */
+    uint32_t maxGlobalCorr;        /* EntryJ capacity of the global list; 0 = 25 * maxKeyframes * (maxKeyframes - 1) / 2 */
+    float colorIntrinsics[16];     /* row-major mat4f of the SIFT image's camera (m_siftIntrinsics) */
+    uint32_t filterIntensity;      /* s_colorFilter analogue m_bFilterIntensity [0] */
+    float intensitySigmaD;         /* m_intensitySigmaD [2.5]; 0 < sigma <= 3.5 (radius ceil(2 sigma) <= 7) when filtering */
+    uint32_t reserved[2];
+} BFBundlerOptions;
+
+#define BF_BUNDLER_NO_FRAME 0xFFFFFFFFu
+#define BF_BUNDLER_LOCAL 0u        /* bf_bundler_matcher / _cache: the local set frames go to */
+#define BF_BUNDLER_OPT_LOCAL 1u    /* the other local set: the last closed submap, or empty */
+#define BF_BUNDLER_GLOBAL 2u
+
+/* What bf_bundler_process_frame reports about one frame (HOST). */
+typedef struct BFBundlerFrame {
+    uint32_t frame, localFrame, submap;     /* index over all frames, inside its submap, and the submap's index */
+    uint32_t numKeys, siftFlags;            /* the detector's count and flags (BF_SIFT_TRUNCATED) */
+    uint32_t valid;                         /* filterFrames' decision (frame 0: 1) */
+    uint32_t lastMatchedLocal;              /* BF_BUNDLER_NO_FRAME if none */
+    uint32_t residualsAdded, residualsTotal;/* EntryJ appended by this frame, and the submap's list length after it */
+    uint32_t submapClosed;                  /* this frame was its submap's last: bf_bundler_submap describes it */
+    float siftPose[16];                     /* d_siftTrajectory[frame] */
+    float integrateTransform[16];           /* m_currIntegrateTransform[frame]; all -inf when invalid */
+} BFBundlerFrame;
+
+/* The last closed submap (HOST record; d_ pointers DEVICE), in the form bf_solver_solve and
+ * bf_recon_set_local_correspondences take. */
+typedef struct BFBundlerSubmap {
+    BFEntryJ* d_corr;                  /* [numCorr] */
+    const uint32_t* d_keyIdx;          /* [numCorr][2]: the records' keys in the local store's linear key array */
+    const int32_t* d_validImages;      /* [numFrames] */
+    const int32_t* validImages;        /* HOST [numFrames] */
+    const BFCachedFrame* cacheFrames;  /* HOST [submapSize + 1] */
+    const BFCachedFrame* d_cacheFrames;/* the same table, DEVICE */
+    uint32_t numCorr, numFrames;
+    uint32_t submap, isValid;          /* Bundler::isValid: an image after the first is valid */
+    uint32_t released, reserved;       /* bf_bundler_fuse_submap / _invalid_submap has taken it */
+} BFBundlerSubmap;
+
+/* What bf_bundler_fuse_submap reports about the key frame it made (HOST). */
+typedef struct BFBundlerKeyframe {
+    uint32_t keyframe, numKeys, numTracks;
+    uint32_t valid;
+    uint32_t lastMatchedGlobal;        /* BF_BUNDLER_NO_FRAME if none */
+    uint32_t residualsAdded, residualsTotal;
+    uint32_t globalTrackingLost;
+} BFBundlerKeyframe;
+
+typedef struct BFBundlerStats {
+    uint64_t frames;       /* bf_bundler_process_frame calls that reached the device */
+    uint64_t hostWaits;    /* times the host waited for the stream inside process_frame / fuse_submap / invalid_submap */
+    uint64_t keyframes;    /* images in the global store (fused or invalid) */
+} BFBundlerStats;
+
 #ifdef __cplusplus
 } /* extern "C" */
 
 static_assert(sizeof(BFSiftOptions) == 48, "BFSiftOptions is 48 B");
+static_assert(sizeof(BFBundlerFrame) == 168, "BFBundlerFrame is 168 B");
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
