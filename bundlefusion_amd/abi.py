@@ -272,6 +272,12 @@ class BFBundlerStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("frames", "hostWaits", "keyframes")]
 
 
+class BFBundlerRetry(C.Structure):  # what the last fuse_submap / retry did about the retry list
+    _fields_ = [(n, C.c_uint32) for n in ("attempted", "candidate", "revalidated", "lastMatchedGlobal", "residualsAdded",
+                                          "residualsTotal", "listLength", "finished", "numSeeds")] + [
+        ("seeds", (C.c_uint32 * 2) * 5), ("reserved", C.c_uint32)]
+
+
 BUNDLER_NO_FRAME, BUNDLER_LOCAL, BUNDLER_OPT_LOCAL, BUNDLER_GLOBAL = 0xFFFFFFFF, 0, 1, 2
 SIFT_LEVELS, SIFT_MAX_FILTER, SIFT_TRUNCATED = 12, 33, 1
 SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
@@ -280,6 +286,7 @@ assert C.sizeof(BFSiftKeyPoint) == 16 and SIFT_KEYPOINT_DTYPE.itemsize == 16
 assert C.sizeof(BFMatchVerifyOptions) == 32
 assert C.sizeof(BFSiftOptions) == 48
 assert C.sizeof(BFBundlerFrame) == 168
+assert C.sizeof(BFBundlerRetry) == 80
 
 
 class BFVoxelOp(C.Structure):  # include/bf/bf.h

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import DeviceArray, check, lib
 from .abi import (BUNDLER_GLOBAL, BUNDLER_LOCAL, BUNDLER_NO_FRAME, BUNDLER_OPT_LOCAL, ENTRYJ_DTYPE, BFBundlerFrame,
-                  BFBundlerKeyframe, BFBundlerOptions, BFBundlerStats, BFBundlerSubmap, BFCacheOptions, BFMatcherOptions,
+                  BFBundlerKeyframe, BFBundlerOptions, BFBundlerRetry, BFBundlerStats, BFBundlerSubmap, BFCacheOptions, BFMatcherOptions,
                   BFMatchVerifyOptions, BFSiftOptions)
 from .cache import CUDACache
 from .match import Matcher
@@ -55,6 +55,13 @@ def _frame_dict(r: BFBundlerFrame) -> dict:
                                          "residualsAdded", "residualsTotal", "submapClosed")}
     d["siftPose"] = np.array(r.siftPose[:], np.float32).reshape(4, 4)
     d["integrateTransform"] = np.array(r.integrateTransform[:], np.float32).reshape(4, 4)
+    return d
+
+
+def _retry_dict(r: BFBundlerRetry) -> dict:
+    d = {n: int(getattr(r, n)) for n in ("attempted", "candidate", "revalidated", "lastMatchedGlobal", "residualsAdded",
+                                         "residualsTotal", "listLength", "finished")}
+    d["seeds"] = [(int(r.seeds[k][0]), int(r.seeds[k][1])) for k in range(r.numSeeds)]
     return d
 
 
@@ -147,6 +154,54 @@ class Bundler:
 
     def invalid_submap(self):
         check(lib().bf_bundler_invalid_submap(self.h))
+
+    # ---- retry (Bundler::tryRevalidation, the retry list, the trajectory seeds) ----
+    def set_retry(self, enable=True):
+        """Off after create. Only before the first key frame; reset keeps it."""
+        check(lib().bf_retry_enable(self.h, C.c_uint32(int(bool(enable)))))
+
+    def retry(self, allow_capacity=False) -> dict:
+        """The sequence-over attempt: one revalidation without a new key frame. BFBundlerRetry as a dict."""
+        r = BFBundlerRetry()
+        rc = lib().bf_retry_attempt(self.h, C.byref(r))
+        if not (allow_capacity and rc == -3):
+            check(rc)
+        d = _retry_dict(r)
+        d["capacity"] = rc == -3
+        return d
+
+    def last_retry(self) -> dict:
+        """What the last fuse_submap or retry did about the list."""
+        r = BFBundlerRetry()
+        check(lib().bf_retry_last(self.h, C.byref(r)))
+        return _retry_dict(r)
+
+    def retry_list(self) -> list:
+        """The key frames waiting for a revalidation, front (the next candidate) first."""
+        n = C.c_uint32()
+        check(lib().bf_retry_list(self.h, None, C.c_uint32(0), C.byref(n)))
+        out = (C.c_uint32 * max(n.value, 1))()
+        check(lib().bf_retry_list(self.h, out, C.c_uint32(n.value), C.byref(n)))
+        return list(out[:n.value])
+
+    def apply_seeds(self, d_T: DeviceArray):
+        """d_T[to] = d_T[from] for the last call's seeds, in order, on the bundler's stream. d_T: [n, 4, 4] float32."""
+        check(lib().bf_retry_apply_seeds(self.h, d_T.ptr, C.c_uint32(int(np.prod(d_T.shape)) // 16)))
+
+    def keyframe_frames(self, k: int) -> np.ndarray:
+        """The valid flags of the submap frames key frame k stands for (empty for an invalid_submap key frame)."""
+        out, n = (C.c_int32 * self.opts.submapSize)(), C.c_uint32()
+        check(lib().bf_retry_keyframe_frames(self.h, C.c_uint32(k), out, C.byref(n)))
+        return np.array(out[:n.value], np.int32)
+
+    def debug_retry_close(self, idx: int, allow_capacity=False) -> dict:
+        r = BFBundlerRetry()
+        rc = lib().bf_retry_debug_close(self.h, C.c_uint32(idx), C.byref(r))
+        if not (allow_capacity and rc == -3):
+            check(rc)
+        d = _retry_dict(r)
+        d["capacity"] = rc == -3
+        return d
 
     def global_list(self) -> dict:
         """corr (EntryJ, host), key_idx [n, 2], prefix [keyframes] and the device pointer of the list."""

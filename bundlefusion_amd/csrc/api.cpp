@@ -211,7 +211,8 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFBundlerFrame", sizeof(BFBundlerFrame)},
         {"BFBundlerSubmap", sizeof(BFBundlerSubmap)},
         {"BFBundlerKeyframe", sizeof(BFBundlerKeyframe)},
-        {"BFBundlerStats", sizeof(BFBundlerStats)}};
+        {"BFBundlerStats", sizeof(BFBundlerStats)},
+        {"BFBundlerRetry", sizeof(BFBundlerRetry)}};
     for (const auto& e : kSizes)
         if (std::strcmp(e.n, name) == 0) {
             *out = e.s;
@@ -1670,6 +1671,49 @@ int bf_bundler_debug_reclose(bf_bundler* b, BFBundlerFrame* out) {
     BF_TRY
     BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
     b->b->debugReclose(out);
+    BF_CATCH
+}
+// retry: every null / range check is the first thing each call does, before any device work
+int bf_retry_enable(bf_bundler* b, uint32_t enable) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->setRetry(enable != 0);
+    BF_CATCH
+}
+int bf_retry_attempt(bf_bundler* b, BFBundlerRetry* out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    b->b->retry(out);
+    BF_CATCH
+}
+int bf_retry_last(bf_bundler* b, BFBundlerRetry* out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    b->b->lastRetry(out);
+    BF_CATCH
+}
+int bf_retry_list(bf_bundler* b, uint32_t* out, uint32_t cap, uint32_t* n) {
+    BF_TRY
+    BF_REQUIRE(b && n && (out || cap == 0), BF_ERR_ARG, "null argument");
+    b->b->retryList(out, cap, n);
+    BF_CATCH
+}
+int bf_retry_apply_seeds(bf_bundler* b, float* d_T, uint32_t numPoses) {
+    BF_TRY
+    BF_REQUIRE(b && d_T, BF_ERR_ARG, "null argument");
+    b->b->applySeeds(d_T, numPoses);
+    BF_CATCH
+}
+int bf_retry_keyframe_frames(bf_bundler* b, uint32_t k, int32_t* valid, uint32_t* n) {
+    BF_TRY
+    BF_REQUIRE(b && valid && n, BF_ERR_ARG, "null argument");
+    b->b->keyframeFrames(k, valid, n);
+    BF_CATCH
+}
+int bf_retry_debug_close(bf_bundler* b, uint32_t idx, BFBundlerRetry* out) {
+    BF_TRY
+    BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
+    b->b->debugRetryClose(idx, out);
     BF_CATCH
 }
 

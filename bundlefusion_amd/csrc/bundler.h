@@ -5,11 +5,17 @@
 // (k_frame_close, k_gauss_intensity) and copies none of the stages'. One stream, no device allocation after the ctor.
 //
 // Host wait budgets (counted in BFBundlerStats.hostWaits): processFrame <= 2 (the detector's key count; the closing
-// launch's record), fuseSubmap <= 2 (the fuse's count read-back; the record), invalidSubmap 0.
+// launch's record), fuseSubmap <= 2 (the fuse's count read-back; the record) and <= 3 with a retry attempt (the
+// candidate's record), retry <= 1, invalidSubmap 0.
+//
+// Retry (Bundler::tryRevalidation, Bundler.cpp:306-352; SIFTImageManager.h:263-271; off unless setRetry): a key frame with
+// keys that matched no earlier one waits on a host deque, front in / front out; a key frame that matched pops one
+// candidate idx and matches it against the LATER images (cur = idx, start = idx + 1), one more closing launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <deque>
 #include <memory>
 #include <vector>
 
@@ -44,7 +50,8 @@ GaussTable intensity_gauss_table(float sigmaD);
 struct CloseRecord {
     uint32_t valid, lastMatched, added, total;
     uint32_t flags;  // 1: the list would pass its capacity, nothing was appended
-    uint32_t seq, pad[2];
+    uint32_t seq;
+    uint32_t cur, start;  // the launch's own image and first prev: a retry launch's record names its candidate
     float sift[16], integ[16];
 };
 
@@ -67,6 +74,14 @@ public:
     void invalidSubmap();
     void global(BFEntryJ** corr, const uint32_t** keyIdx, uint32_t* n, const uint32_t** prefix, uint32_t* numKeyframes);
     void debugReclose(BFBundlerFrame* out);
+    // retry
+    void setRetry(bool on);
+    void retry(BFBundlerRetry* out);  // the sequence-over attempt (OnlineBundler.cpp:287-296)
+    void lastRetry(BFBundlerRetry* out) const;
+    void retryList(uint32_t* out, uint32_t cap, uint32_t* n) const;
+    void applySeeds(float* dT, uint32_t numPoses);
+    void keyframeFrames(uint32_t k, int32_t* valid, uint32_t* n) const;
+    void debugRetryClose(uint32_t idx, BFBundlerRetry* out);
 
     const BundlerConfig& config() const { return cfg_; }
     hipStream_t stream() const { return stream_; }
@@ -78,7 +93,18 @@ public:
 
 private:
     // one launch of k_frame_close for image `cur` of matcher m on list `list` (0 / 1 local, 2 global), then the wait
-    void closeFrame(Matcher& m, uint32_t list, uint32_t cur, bool chain, uint32_t frameAll);
+    // over prev in [start, n)
+    void closeFrame(Matcher& m, uint32_t list, uint32_t cur, uint32_t start, bool chain, uint32_t frameAll);
+    // Bundler::matchAndFilter up to filterFrames for image cur of the global store
+    void matchGlobal(uint32_t cur, uint32_t start);
+    // tryRevalidation's body for candidate idx: [the filter chain,] the closing launch, last_ and the seeds. The list
+    // is the caller's. True: the launch reported an overflow.
+    bool revalidate(uint32_t idx, bool filters);
+    bool tryRevalidation(bool scanDone);  // pops, revalidates, pushes back on failure; true: overflow
+    void addSeeds(uint32_t cur, uint32_t lastMatched);
+    void pushSeed(uint32_t to, uint32_t from);
+    void beginRetryReport();
+    void endRetryReport();
     void fillFrame(BFBundlerFrame* out, uint32_t lf, bool closed) const;
     void wait();  // the stream, counted
 
@@ -116,6 +142,12 @@ private:
     uint32_t lastBefore_ = 0;
     bool canReclose_ = false;
     std::vector<uint32_t> prefix_;
+    // retry
+    bool retry_ = false;
+    std::deque<uint32_t> retryList_;     // m_imagesToRetry
+    int64_t continueRetry_ = 0;          // m_continueRetry: 0 unset, > 0 the first candidate after the sequence ended, -1 done
+    BFBundlerRetry last_{};              // what the last fuseSubmap / retry did
+    std::vector<std::vector<int32_t>> keyframeValid_;  // m_localTrajectoriesValid
     BFBundlerStats stats_{};
 };
 

@@ -23,9 +23,14 @@
 //      float4x4::getInverse is not in the reference tree, and a sift pose is a product of rigid Kabsch transforms.
 //   5. the record, into pinned host memory (lane 0 the words, lanes 0..15 the matrices), then a system-scope fence.
 // No float atomics, no scratch (the matrices live in LDS, every index into a per-lane array is a constant).
+// The retry launch (Bundler::tryRevalidation, Bundler.cpp:306-352) is the same kernel for a key frame in the middle of
+// the global store: cur = idx, start = idx + 1, no chain. Every pass walks rounds of 64 images from `start`, lane l of a
+// round owns prev = r0 + l in both, nothing below `start` is read (those counts belong to the current key frame's own
+// match), and the records it appends are {imgIdx_i = prev > idx, imgIdx_j = idx}.
 // k_gauss_intensity — one lane per pixel; window clipped at the borders; sum order m (x) outer, n (y) inner.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -101,8 +106,8 @@ __global__ __launch_bounds__(64) void k_frame_close(CloseArgs A) {
     int i = -1;  // step 4's prev: from cur - 1 down to the first filtered count > 0
     if (A.chain && valid) {
         i = (int)A.cur - 1;
-        while (i >= 0 && A.v.filtCount[i] == 0) i--;  // wave-uniform
-        if (i < 0) valid = false;                     // cur is not the last image: no chain, as an unmatched frame
+        while (i >= (int)A.start && A.v.filtCount[i] == 0) i--;  // wave-uniform; a count below start is another launch's
+        if (i < (int)A.start) valid = false;  // cur is not the last image: no chain, as an unmatched frame
     }
 
     // 3: AddCurrToResidualsCU
@@ -202,6 +207,8 @@ __global__ __launch_bounds__(64) void k_frame_close(CloseArgs A) {
         A.rec->total = listEnd + (valid ? added : 0u);
         A.rec->flags = overflow ? Bundler::kOverflow : 0u;
         A.rec->seq = A.seq;
+        A.rec->cur = A.cur;
+        A.rec->start = A.start;
     }
     __threadfence_system();
 }
@@ -402,14 +409,19 @@ void Bundler::reset() {
     released_ = true;
     canReclose_ = false;
     prefix_.clear();
+    retryList_.clear();  // retry_ itself is a setting and stays
+    continueRetry_ = 0;
+    keyframeValid_.clear();
+    beginRetryReport();
     stats_ = BFBundlerStats{};
 }
 
-void Bundler::closeFrame(Matcher& m, uint32_t list, uint32_t cur, bool chain, uint32_t frameAll) {
+void Bundler::closeFrame(Matcher& m, uint32_t list, uint32_t cur, uint32_t start, bool chain, uint32_t frameAll) {
+    BF_REQUIRE(!chain || start == 0, BF_ERR_INTERNAL, "the sift chain walks from frame 0: a local close starts at 0");
     CloseArgs A{};
-    A.v = m.prepareClose(cur, 0);
+    A.v = m.prepareClose(cur, start);
     A.cur = cur;
-    A.start = 0;  // numFrames == curFrame + 1 always: there is no retry frame (Bundler.cpp:112)
+    A.start = start;  // 0 for a current frame, cur + 1 for a retry frame (Bundler.cpp:112)
     A.n = m.numImages();
     A.corr = corr_[list].p;
     A.keyIdx = keyIdx_[list].p;
@@ -492,7 +504,7 @@ void Bundler::processFrame(const uint8_t* color, uint32_t cw, uint32_t ch, const
         M.filterSurfaceArea(lf, 0, cfg_.verify);
         M.filterDenseVerify(lf, 0, frameTab_[cur_].p, S + 1, C.config().width, C.config().height, C.intrinsics(), cfg_.verify);
         lastBefore_ = total_[cur_];
-        closeFrame(M, cur_, lf, true, f);
+        closeFrame(M, cur_, lf, 0, true, f);
         overflow = (rec_->flags & kOverflow) != 0;
         fillFrame(out, lf, closes);
     } else {  // the very first frame: both trajectories start at the identity (OnlineBundler.cpp:66-74)
@@ -538,7 +550,7 @@ void Bundler::debugReclose(BFBundlerFrame* out) {
     BF_HIP(hipMemcpyAsync(counts_.p + cur_, &rec_->total, 4, hipMemcpyHostToDevice, stream_));
     BF_HIP(hipStreamSynchronize(stream_));
     total_[cur_] = lastBefore_;
-    closeFrame(M, cur_, lastFrame_.localFrame, true, lastFrame_.frame);
+    closeFrame(M, cur_, lastFrame_.localFrame, 0, true, lastFrame_.frame);
     const bool overflow = (rec_->flags & kOverflow) != 0;
     *out = lastFrame_;
     fillFrame(out, lastFrame_.localFrame, false);
@@ -584,6 +596,10 @@ void Bundler::fuseSubmap(const float* localTransforms, BFBundlerKeyframe* out) {
     glob_->streamDrained();
     cacheGlob_->copyFrameFrom(*cacheLoc_[closed_], 0);
     stats_.keyframes++;
+    // m_localTrajectoriesValid[curGlobalFrame] (OnlineBundler.cpp:321)
+    keyframeValid_.resize(idx + 1);
+    keyframeValid_[idx].assign(closedValidImages_.begin(), closedValidImages_.begin() + std::min(cfg_.submapSize, closedFrames_));
+    beginRetryReport();
     std::memset(out, 0, sizeof(*out));
     out->keyframe = idx;
     out->numKeys = nk;
@@ -591,23 +607,28 @@ void Bundler::fuseSubmap(const float* localTransforms, BFBundlerKeyframe* out) {
     out->valid = 1;
     out->lastMatchedGlobal = kNone;
     out->residualsTotal = total_[2];
-    bool overflow = false;
+    bool overflow = false, retryOverflow = false;
     if (glob_->numImages() > 1) {
-        Cache& G = *cacheGlob_;
-        glob_->match(idx, 0);
-        glob_->filter(idx, 0);
-        glob_->filterSurfaceArea(idx, 0, cfg_.verify);
-        glob_->filterDenseVerify(idx, 0, frameTab_[2].p, cfg_.maxKeyframes, G.config().width, G.config().height, G.intrinsics(), cfg_.verify);
-        closeFrame(*glob_, 2, idx, false, 0);
+        matchGlobal(idx, 0);
+        closeFrame(*glob_, 2, idx, 0, false, 0);
         overflow = (rec_->flags & kOverflow) != 0;
         out->valid = rec_->valid;
         out->lastMatchedGlobal = rec_->lastMatched;
         out->residualsAdded = rec_->added;
         out->residualsTotal = rec_->total;
         out->globalTrackingLost = rec_->valid ? 0u : 1u;
+        if (retry_) {  // Bundler.cpp:223-237
+            if (rec_->valid) {
+                addSeeds(idx, rec_->lastMatched);
+                retryOverflow = tryRevalidation(false);  // one revalidation per key frame
+            } else if (nk > 0) {
+                retryList_.push_front(idx);
+            }
+        }
     }
     prefix_.resize(idx + 1, prefix_.empty() ? 0u : prefix_.back());
     prefix_[idx] = total_[2];
+    endRetryReport();
     // done with local data (OnlineBundler.cpp:324)
     L.reset();
     cacheLoc_[closed_]->reset();
@@ -616,6 +637,138 @@ void Bundler::fuseSubmap(const float* localTransforms, BFBundlerKeyframe* out) {
     free_[closed_] = true;
     released_ = true;
     BF_REQUIRE(!overflow, BF_ERR_CAPACITY, "fuse_submap: the key frame's residuals would pass maxGlobalCorr; none was appended");
+    BF_REQUIRE(!retryOverflow, BF_ERR_CAPACITY, "fuse_submap: the retry candidate's residuals would pass maxGlobalCorr; none was appended");
+}
+
+// ---- retry: Bundler::tryRevalidation (Bundler.cpp:306-352), the list of SIFTImageManager.h:263-271 ------------------------
+void Bundler::matchGlobal(uint32_t cur, uint32_t start) {
+    Cache& G = *cacheGlob_;
+    glob_->match(cur, start);
+    glob_->filter(cur, start);
+    glob_->filterSurfaceArea(cur, start, cfg_.verify);
+    glob_->filterDenseVerify(cur, start, frameTab_[2].p, cfg_.maxKeyframes, G.config().width, G.config().height, G.intrinsics(), cfg_.verify);
+}
+
+void Bundler::beginRetryReport() {
+    last_ = BFBundlerRetry{};
+    last_.candidate = last_.revalidated = last_.lastMatchedGlobal = kNone;
+}
+
+void Bundler::endRetryReport() {
+    last_.residualsTotal = total_[2];
+    last_.listLength = (uint32_t)retryList_.size();
+    last_.finished = continueRetry_ < 0 ? 1u : 0u;
+}
+
+void Bundler::pushSeed(uint32_t to, uint32_t from) {
+    if (to >= cfg_.maxKeyframes || last_.numSeeds >= 5) return;  // d_trajectory has maxKeyframes poses
+    last_.seeds[last_.numSeeds][0] = to;
+    last_.seeds[last_.numSeeds][1] = from;
+    last_.numSeeds++;
+}
+
+void Bundler::addSeeds(uint32_t cur, uint32_t lastMatched) {
+    if (lastMatched + 1 == cur) return;  // re-initialize to a better location based off of the last match
+    pushSeed(cur, lastMatched);
+    pushSeed(cur + 1, lastMatched);
+}
+
+bool Bundler::revalidate(uint32_t idx, bool filters) {
+    const uint32_t n = glob_->numImages();
+    // an entry equal to the last key frame is a current frame: matched against the earlier images, once
+    const uint32_t start = idx + 1 == n ? 0 : idx + 1;
+    if (filters) matchGlobal(idx, start);
+    closeFrame(*glob_, 2, idx, start, false, 0);
+    last_.attempted = 1;
+    last_.candidate = idx;
+    if (rec_->valid) {
+        last_.revalidated = idx;
+        last_.lastMatchedGlobal = rec_->lastMatched;
+        last_.residualsAdded = rec_->added;
+        addSeeds(idx, rec_->lastMatched);
+        pushSeed(idx, rec_->lastMatched);  // Bundler.cpp:330
+    }
+    return (rec_->flags & kOverflow) != 0;
+}
+
+bool Bundler::tryRevalidation(bool scanDone) {
+    if (continueRetry_ < 0 || retryList_.empty()) return false;  // nothing to do
+    const uint32_t idx = retryList_.front();
+    retryList_.pop_front();
+    if (scanDone) {
+        if (continueRetry_ == 0) {
+            continueRetry_ = idx;
+        } else if (continueRetry_ == (int64_t)idx) {
+            continueRetry_ = -1;  // looped around again: nothing more to do
+            return false;
+        }
+    }
+    const bool overflow = revalidate(idx, true);
+    if (last_.revalidated != idx) retryList_.push_front(idx);
+    return overflow;
+}
+
+void Bundler::setRetry(bool on) {
+    BF_REQUIRE(glob_->numImages() == 0, BF_ERR_STATE, "set_retry: a key frame exists");
+    retry_ = on;
+}
+
+void Bundler::retry(BFBundlerRetry* out) {
+    BF_REQUIRE(out != nullptr, BF_ERR_ARG, "retry: null output");
+    BF_REQUIRE(retry_, BF_ERR_STATE, "retry: retry is off (bf_retry_enable)");
+    BF_REQUIRE(closed_ < 0 || released_, BF_ERR_STATE, "retry: a closed submap waits for fuse_submap / invalid_submap");
+    beginRetryReport();
+    const bool overflow = tryRevalidation(true);
+    if (!prefix_.empty()) prefix_.back() = total_[2];
+    endRetryReport();
+    *out = last_;
+    BF_REQUIRE(!overflow, BF_ERR_CAPACITY, "retry: the candidate's residuals would pass maxGlobalCorr; none was appended");
+}
+
+void Bundler::lastRetry(BFBundlerRetry* out) const {
+    BF_REQUIRE(out != nullptr, BF_ERR_ARG, "last_retry: null output");
+    *out = last_;
+}
+
+void Bundler::retryList(uint32_t* out, uint32_t cap, uint32_t* n) const {
+    BF_REQUIRE(n != nullptr && (out != nullptr || cap == 0), BF_ERR_ARG, "retry_list: null output");
+    *n = (uint32_t)retryList_.size();
+    for (uint32_t k = 0; k < cap && k < retryList_.size(); k++) out[k] = retryList_[k];
+}
+
+void Bundler::applySeeds(float* dT, uint32_t numPoses) {
+    BF_REQUIRE(dT != nullptr, BF_ERR_ARG, "apply_seeds: null trajectory");
+    for (uint32_t k = 0; k < last_.numSeeds; k++)
+        BF_REQUIRE(last_.seeds[k][0] < numPoses && last_.seeds[k][1] < numPoses, BF_ERR_ARG, "apply_seeds: a seed names a pose >= numPoses");
+    for (uint32_t k = 0; k < last_.numSeeds; k++)
+        BF_HIP(hipMemcpyAsync(dT + 16 * (size_t)last_.seeds[k][0], dT + 16 * (size_t)last_.seeds[k][1], 64, hipMemcpyDeviceToDevice, stream_));
+}
+
+void Bundler::keyframeFrames(uint32_t k, int32_t* valid, uint32_t* n) const {
+    BF_REQUIRE(valid != nullptr && n != nullptr, BF_ERR_ARG, "keyframe_frames: null output");
+    BF_REQUIRE(k < keyframeValid_.size(), BF_ERR_ARG, "keyframe_frames: k >= the number of key frames");
+    *n = (uint32_t)keyframeValid_[k].size();
+    for (uint32_t i = 0; i < *n; i++) valid[i] = keyframeValid_[k][i];
+}
+
+void Bundler::debugRetryClose(uint32_t idx, BFBundlerRetry* out) {
+    BF_REQUIRE(out != nullptr, BF_ERR_ARG, "debug_retry_close: null output");
+    const uint32_t n = glob_->numImages();
+    BF_REQUIRE(idx < n, BF_ERR_ARG, "debug_retry_close: idx >= the number of key frames");
+    BF_REQUIRE(retry_ && (closed_ < 0 || released_) && idx >= 1 && idx + 1 < n && glob_->valid(idx) == 0, BF_ERR_STATE,
+               "debug_retry_close: retry on, no closed submap waiting, and idx an invalid key frame in [1, n - 1)");
+    beginRetryReport();
+    const bool overflow = revalidate(idx, false);
+    if (last_.revalidated == idx)
+        for (auto it = retryList_.begin(); it != retryList_.end(); ++it)
+            if (*it == idx) {
+                retryList_.erase(it);
+                break;
+            }
+    prefix_.back() = total_[2];
+    endRetryReport();
+    *out = last_;
+    BF_REQUIRE(!overflow, BF_ERR_CAPACITY, "debug_retry_close: the candidate's residuals would pass maxGlobalCorr; none was appended");
 }
 
 void Bundler::invalidSubmap() {
@@ -626,6 +779,7 @@ void Bundler::invalidSubmap() {
     const uint32_t idx = glob_->addImage(nullptr, nullptr, 0);
     if (idx > 0) glob_->setValid(idx, 0);
     stats_.keyframes++;
+    keyframeValid_.resize(idx + 1);  // no frames: the INVALIDATE branch records none (OnlineBundler.cpp:351-360)
     prefix_.resize(idx + 1, prefix_.empty() ? 0u : prefix_.back());
     prefix_[idx] = total_[2];
     loc_[closed_]->reset();

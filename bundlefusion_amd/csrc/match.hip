@@ -5,7 +5,8 @@
 //   SiftGPU/SIFTImageManager.cu:59-607, 610-687, SiftGPU/SIFTImageManager.cpp:44-83, 551-575,
 //   SiftGPU/cuda_kabsch.h:73-229, 281-502, SiftGPU/cuda_surfaceArea.h, SiftGPU/cuda_SVD.h:17-213,
 //   SiftGPU/cuda_EigenValue.h:56-85.
-// The DoG detector / descriptor and tryRevalidation are not here; fuseToGlobal is match_fuse.h, included at the end.
+// The DoG detector / descriptor is sift.hip, tryRevalidation is the bundler's (bundler.hip); fuseToGlobal is
+// match_fuse.h, included at the end.
 //
 // k_match — one workgroup (4 waves) per image pair (prev, cur), every pair of a call in one launch. The reference
 // writes the num1 x num2 int32 dot matrix to memory and reduces it with two more kernels per pair; here it never

@@ -611,8 +611,8 @@ int bf_corr_from_depth(const float* const* depth, const float* transforms, const
 /* ---- sparse matcher: the matching side of SIFTImageManager + SiftMatch + Bundler::matchAndFilter ----------
  * Key points and 128-byte descriptors of any detector in, EntryJ and pair transforms out, through the reference's whole
  * filter chain: Kabsch, surface area, dense verify, filterFrames, and a solved submap's tracks fused into the keys of
- * its global image (bf_match_fuse_to_global). The DoG detector / descriptor is bf_sift_* below; tryRevalidation is not
- * part of it.
+ * its global image (bf_match_fuse_to_global). The DoG detector / descriptor is bf_sift_* below; tryRevalidation drives
+ * these calls with curFrame in the middle of the store and is the bundler's (bf_retry_* below).
  * Work is queued on the matcher's own stream; the read-backs and bf_matcher_filter_frames / _add_to_residuals
  * wait for it. No device allocation after bf_matcher_create. Per-pair results are indexed by the earlier image
  * `prev`, as the reference's d_curr* arrays are, and hold the last bf_matcher_match / _filter.
@@ -818,9 +818,12 @@ int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
  *   bf_bundler_process_frame  <= 2: the detector's key count (the store's host table needs it, as
  *                                   finalizeSIFTImageGPU does), and the record (none for frame 0);
  *   bf_bundler_fuse_submap    <= 2: the fuse's count read-back, and the record (none for the first key frame);
+ *                             <= 3 with retry on, when a candidate is tried: its record;
+ *   bf_retry_attempt          <= 1: the candidate's record (none when there is nothing to do);
  *   bf_bundler_invalid_submap    0.
- * Out of scope, as DESIGN.md §7 lists: tryRevalidation, the retry list, the global-only trajectory re-initialisation
- * (Bundler.cpp:223-237). DESIGN.md §3.7 has the semantics and the departures. */
+ * tryRevalidation, the retry list and the global-only trajectory re-initialisation (Bundler.cpp:223-237, 306-352; the
+ * reference's USE_RETRY) are OFF unless bf_retry_enable turns them on; with retry off every call behaves and waits
+ * as it did before they existed. DESIGN.md §3.7 has the semantics and the departures. */
 typedef struct bf_bundler bf_bundler;
 /* OnlineBundler::OnlineBundler (OnlineBundler.cpp:31-91) + Bundler::Bundler x 3 (Bundler.cpp:19-54). Host checks first,
  * each BF_ERR_ARG and before any device work: null argument; submapSize 0; maxKeyframes < 2; submapSize * maxKeyframes or a
@@ -867,9 +870,13 @@ int bf_bundler_fuse_submap(bf_bundler* b, const float* d_localTransforms, BFBund
 /* ... state INVALIDATE (OnlineBundler.cpp:351-360): Bundler::addInvalidFrame (Bundler.cpp:362-368: an image without keys,
  * bf_cache_increment) and the reset of the closed local set. BF_ERR_STATE: no closed submap waits. */
 int bf_bundler_invalid_submap(bf_bundler* b);
-/* The global list in the form bf_recon_set_global_correspondences takes: DEVICE EntryJ[*n], HOST prefix[*numKeyframes]
- * (prefix[k] = entries with max(i, j) <= k). A key frame k is only paired with prev < k, so the list is ordered by
- * max(i, j) by construction. Any output may be NULL. Valid until the next bf_bundler_fuse_submap / _invalid_submap. */
+/* The global list in the form bf_recon_set_global_correspondences takes: DEVICE EntryJ[*n], HOST prefix[*numKeyframes].
+ * prefix[k] = the list's length after key frame k was fused, a retry candidate's records in that call included: it
+ * ascends, ends at *n, and every record below prefix[k] names images <= k only. With retry off a key frame k is only
+ * paired with prev < k, so the list is ordered by max(i, j) and prefix[k] = entries with max(i, j) <= k; with retry on a
+ * revalidated key frame idx adds records {imgIdx_i = prev > idx, imgIdx_j = idx} at the list's end, and a
+ * bf_retry_attempt that appends moves the last prefix[] entry. Any output may be NULL. Valid until the next
+ * bf_bundler_fuse_submap / _invalid_submap / _retry. */
 int bf_bundler_global(bf_bundler* b, BFEntryJ** d_corr, const uint32_t** d_keyIdx, uint32_t* n, const uint32_t** prefix,
                       uint32_t* numKeyframes);
 /* BORROWED handles of the stages, for the read-backs that exist (bf_matcher_filtered_matches, bf_match_image_keys,
@@ -886,6 +893,38 @@ int bf_bundler_stats(bf_bundler* b, BFBundlerStats* out);
  * (after bf_match_debug_set_filtered on the borrowed local matcher). Only right after a bf_bundler_process_frame of a
  * local frame > 0 that did not close a submap, else BF_ERR_STATE. */
 int bf_bundler_debug_reclose(bf_bundler* b, BFBundlerFrame* out);
+/* ---- retry: Bundler::tryRevalidation (Bundler.cpp:306-352), the retry list (SIFTImageManager.h:263-271) and the
+ * global-only trajectory re-initialisation (Bundler.cpp:223-237). Global role only. The list is a host deque, pushed and
+ * popped at the FRONT as the reference's: the most recently lost key frame is tried first. With retry on,
+ * bf_bundler_fuse_submap puts a key frame that has keys and matched no earlier key frame on the list; a key frame that
+ * matched pops one candidate idx, runs the whole matchAndFilter chain for curFrame = idx, startFrame = idx + 1 on the
+ * global store and one more closing launch, which appends records {imgIdx_i = prev > idx, imgIdx_j = idx}. A candidate
+ * that matched becomes a valid image; one that did not goes back to the front. A candidate whose records would pass
+ * maxGlobalCorr stays invalid and on the list, and the call returns BF_ERR_CAPACITY after filling its outputs.
+ * enable != 0 turns it on. BF_ERR_STATE once a key frame exists. bf_bundler_reset keeps the setting, empties the list. */
+int bf_retry_enable(bf_bundler* b, uint32_t enable);
+/* The sequence-over attempt (OnlineBundler.cpp:287-296, tryRevalidation with bIsScanDone): one revalidation without a
+ * new key frame. The first candidate popped by this call is remembered; popping it again ends retrying for good
+ * (out->finished; that candidate is dropped as the reference drops it) and later calls, bf_bundler_fuse_submap's
+ * attempts included, do nothing and wait for nothing. A candidate equal to the last key frame is matched as a current
+ * frame (startFrame 0), once. *out (HOST, required) is filled. BF_ERR_STATE: retry is off, or a closed submap waits. */
+int bf_retry_attempt(bf_bundler* b, BFBundlerRetry* out);
+/* What the last bf_bundler_fuse_submap or bf_retry_attempt did (attempted 0 and no seeds after create / reset). */
+int bf_retry_last(bf_bundler* b, BFBundlerRetry* out);
+/* The retry list, front first: min(cap, *n) indices to out (HOST; may be NULL when cap is 0), the length to *n. */
+int bf_retry_list(bf_bundler* b, uint32_t* out, uint32_t cap, uint32_t* n);
+/* The seeds of the last call applied to d_T DEVICE float[numPoses][16], in their order, as device-to-device copies on
+ * the bundler's stream (d_T[to] = d_T[from]). BF_ERR_ARG before any copy: d_T NULL, or a seed naming a pose >= numPoses. */
+int bf_retry_apply_seeds(bf_bundler* b, float* d_T, uint32_t numPoses);
+/* m_localTrajectoriesValid[k] (OnlineBundler.cpp:321): the valid flags of the first min(submapSize, numFrames) frames of
+ * the submap key frame k was fused from, to valid (HOST int32[submapSize]) and their number to *n; 0 for a key frame made
+ * by bf_bundler_invalid_submap. What validateImages walks after a revalidation (:341-344). BF_ERR_ARG: k is no key frame. */
+int bf_retry_keyframe_frames(bf_bundler* b, uint32_t k, int32_t* valid, uint32_t* n);
+/* test entry of the retry closing launch: the launch alone (cur = idx, start = idx + 1, no matching) for key frame idx,
+ * after bf_match_debug_set_filtered / bf_matcher_set_valid on the borrowed global matcher; the outcome is applied as a
+ * revalidation's (valid flag, list, prefix[]) but a failed idx is not put on the list. BF_ERR_ARG: idx is no key frame.
+ * BF_ERR_STATE unless retry is on, no closed submap waits, 1 <= idx < numKeyframes - 1 and image idx is invalid. */
+int bf_retry_debug_close(bf_bundler* b, uint32_t idx, BFBundlerRetry* out);
 
 /* test entry of the workgroup scan and ballot compaction that the compaction kernels share (csrc/wave.h): ONE workgroup
  * of wg lanes (256, 512 or 1024, else BF_ERR_ARG) walks d_in[n] in rounds of wg with a carry. flags == 0: d_out[i] =

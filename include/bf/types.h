@@ -400,9 +400,26 @@ typedef struct BFBundlerKeyframe {
     uint32_t globalTrackingLost;
 } BFBundlerKeyframe;
 
+/* What the last bf_bundler_fuse_submap or bf_retry_attempt did about the retry list (HOST; Bundler::tryRevalidation,
+ * Bundler.cpp:306-352). seeds: the reference's d_trajectory copies of that call as ordered (to, from) key frame pairs,
+ * the current key frame's first (Bundler.cpp:224-227), then the candidate's and Bundler.cpp:330; a `to` at or above
+ * maxKeyframes is dropped. */
+typedef struct BFBundlerRetry {
+    uint32_t attempted;                /* a candidate was popped and its closing launch ran */
+    uint32_t candidate;                /* BF_BUNDLER_NO_FRAME if none */
+    uint32_t revalidated;              /* = candidate when it matched a later key frame, else BF_BUNDLER_NO_FRAME */
+    uint32_t lastMatchedGlobal;        /* the candidate's last matched key frame; BF_BUNDLER_NO_FRAME if none */
+    uint32_t residualsAdded, residualsTotal; /* EntryJ appended for the candidate, and the global list's length */
+    uint32_t listLength;               /* the retry list after the call */
+    uint32_t finished;                 /* the loop-around stop has ended retrying for good */
+    uint32_t numSeeds;
+    uint32_t seeds[5][2];
+    uint32_t reserved;
+} BFBundlerRetry;
+
 typedef struct BFBundlerStats {
     uint64_t frames;       /* bf_bundler_process_frame calls that reached the device */
-    uint64_t hostWaits;    /* times the host waited for the stream inside process_frame / fuse_submap / invalid_submap */
+    uint64_t hostWaits;    /* times the host waited for the stream inside process_frame / fuse_submap / invalid_submap / bf_retry_* */
     uint64_t keyframes;    /* images in the global store (fused or invalid) */
 } BFBundlerStats;
 
@@ -411,6 +428,7 @@ typedef struct BFBundlerStats {
 
 static_assert(sizeof(BFSiftOptions) == 48, "BFSiftOptions is 48 B");
 static_assert(sizeof(BFBundlerFrame) == 168, "BFBundlerFrame is 168 B");
+static_assert(sizeof(BFBundlerRetry) == 80, "BFBundlerRetry is 80 B");
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
