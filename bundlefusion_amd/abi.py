@@ -343,7 +343,7 @@ class BFAppOptions(C.Structure):  # include/bf/bf.h: the FriedLiver application 
                 ("corrStride", C.c_uint32), ("corrDepthThresh", C.c_float), ("prefetchFrames", C.c_uint32),
                 ("decodeThreads", C.c_uint32), ("numSolveFramesBeforeExit", C.c_int32),
                 ("shardCount", C.c_uint32), ("shardIndex", C.c_uint32), ("shardChunk", C.c_float),
-                ("resultLag", C.c_uint32), ("bundlingPriority", C.c_int32)]
+                ("resultLag", C.c_uint32)]
 
 
 class BFAppInfo(C.Structure):

@@ -36,7 +36,7 @@ public:
             if (n) fn(0, n);
             return;
         }
-        std::unique_lock<std::mutex> serial(run_);  // one parallel_for at a time (frame and bundling threads)
+        std::unique_lock<std::mutex> serial(run_);  // one parallel_for at a time (the loops of several ranks share the pool)
         const size_t chunk = (n + t - 1) / t;
         {
             std::lock_guard<std::mutex> lk(mu_);

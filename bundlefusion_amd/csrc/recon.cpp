@@ -90,36 +90,16 @@ Recon::Recon(const BFHashParams& hp, const BFSceneOptions* so, const BFDepthCame
     // a full result ring (RING submaps in flight) hands the oldest result over early, so a lag beyond
     // RING submaps could not be kept exactly
     BF_REQUIRE(opt_.resultLag <= RING * S, BF_ERR_ARG, "resultLag exceeds the result ring (8 submaps)");
+    BF_REQUIRE(o.bundlingPriority == 0, BF_ERR_ARG, "bundlingPriority is reserved and must be 0");
     const uint32_t maxSubmaps = (opt_.maxFrames + S - 1) / S;
     opt_.maxKeyframes = std::max(or_default(o.maxKeyframes, maxSubmaps + 1), 2u);
     opt_.maxLocalCorr = or_default(o.maxLocalCorr, (S + 1) * S / 2 * 25u);
     opt_.maxGlobalCorr = or_default(o.maxGlobalCorr, opt_.maxKeyframes * 1000u);
 
-    // bundling stream priority (BFReconOptions.bundlingPriority): normal (as the scene stream) by default since
-    // the voxel pass runs in resident rounds (Scene::Scene); 1: high throughout; 2: round 4's policy keyed on each
-    // solve's size (switchBundlingPriority). (The scene stream itself at the highest priority measured slower:
-    // 1 517 -> 1 499-1 502 frames/s at the bench workload, config 4's stream 1 103 -> 1 055.)
-    sharded_ = so && so->shardCount > 1;
-    int prLeast = 0, prGreatest = 0;
-    BF_HIP(hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest));
+    // the scene stream and both bundling streams at normal queue priority (rejected experiments)
     BF_HIP(hipStreamCreateWithFlags(&sceneStream_, hipStreamNonBlocking));
-    BF_REQUIRE(o.bundlingPriority >= 0 && o.bundlingPriority <= 2, BF_ERR_ARG, "bundlingPriority 0..2");
-    const bool keyed = o.bundlingPriority == 2;
-    const bool forced = !keyed;
-    if (forced) priorityPolicy_ = o.bundlingPriority;
-    const bool needHigh = forced ? priorityPolicy_ == 1 : true;
-    const bool needNormal = forced ? priorityPolicy_ == 0 : (!sharded_ && opt_.maxKeyframes > kHighPriorityMaxKeyframes);
-    if (needHigh) {
-        BF_HIP(hipStreamCreateWithPriority(&baStreamHi_, hipStreamNonBlocking, prGreatest));
-        BF_HIP(hipStreamCreateWithPriority(&localStreamHi_, hipStreamNonBlocking, prGreatest));
-    }
-    if (needNormal) {  // normal priority, as the scene stream (ROCm's "least" priority is below normal)
-        BF_HIP(hipStreamCreateWithFlags(&baStreamLo_, hipStreamNonBlocking));
-        BF_HIP(hipStreamCreateWithFlags(&localStreamLo_, hipStreamNonBlocking));
-    }
-    baHigh_ = needHigh;
-    baStream_ = baHigh_ ? baStreamHi_ : baStreamLo_;
-    localStream_ = baHigh_ ? localStreamHi_ : localStreamLo_;
+    BF_HIP(hipStreamCreateWithFlags(&baStream_, hipStreamNonBlocking));
+    BF_HIP(hipStreamCreateWithFlags(&localStream_, hipStreamNonBlocking));
     for (int b = 0; b < 2; b++) {
         BF_HIP(hipEventCreateWithFlags(&localDone_[b], hipEventDisableTiming));
         BF_HIP(hipEventCreateWithFlags(&globalDone_[b], hipEventDisableTiming));
@@ -185,10 +165,6 @@ Recon::Recon(const BFHashParams& hp, const BFSceneOptions* so, const BFDepthCame
     BF_HIP(hipMemsetAsync(dGlobalTrans_.p, 0, dGlobalTrans_.bytes(), baStream_));
     BF_HIP(hipStreamSynchronize(baStream_));
 
-    // asyncBundling 2: the solves are issued from a bundling thread (measured: no gain in the bench, the
-    // scene stream stays fed either way)
-    baThreaded_ = opt_.asyncBundling == 2;
-    if (baThreaded_) baThread_ = std::thread([this] { baLoop(); });
     ring_.resize(RING);
     for (Pending& p : ring_) {
         BF_HIP(hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
@@ -204,16 +180,7 @@ Recon::Recon(const BFHashParams& hp, const BFSceneOptions* so, const BFDepthCame
 }
 
 Recon::~Recon() {
-    if (baThread_.joinable()) {
-        {
-            std::lock_guard<std::mutex> lk(baMu_);
-            baStop_ = true;
-        }
-        baCv_.notify_all();
-        baThread_.join();
-    }
-    if (sceneStream_) (void)hipStreamSynchronize(sceneStream_);
-    for (hipStream_t st : {baStreamHi_, baStreamLo_, localStreamHi_, localStreamLo_})
+    for (hipStream_t st : {sceneStream_, baStream_, localStream_})
         if (st) (void)hipStreamSynchronize(st);
     for (int b = 0; b < 2; b++) {
         if (localDone_[b]) (void)hipEventDestroy(localDone_[b]);
@@ -232,10 +199,8 @@ Recon::~Recon() {
     scene_.reset();
     local_.reset();
     global_.reset();
-    if (sceneStream_) (void)hipStreamDestroy(sceneStream_);
-    for (hipStream_t st : {baStreamHi_, baStreamLo_, localStreamHi_, localStreamLo_})
+    for (hipStream_t st : {sceneStream_, baStream_, localStream_, copyStream_})
         if (st) (void)hipStreamDestroy(st);
-    if (copyStream_) (void)hipStreamDestroy(copyStream_);
 }
 
 void Recon::setFrame(uint32_t f, const float* depth, const uint8_t* color, const BFCachedFrame* cache, const BFMat4& Tinc) {
@@ -291,11 +256,10 @@ void Recon::setComm(Comm* c) {
 // same count on every rank: the distinct image pairs of every keyframe prefix, counted from the entries
 // as they were handed over (removals and the per-image cap only ever drop pairs, so these counts bound
 // every later solve). append: the list only grew since the last count (the app's per-keyframe appends),
-// so only the new entries are read, which no solve touches yet (a submap's issue captures the list
-// length of its own frame); otherwise everything is recounted after the bundling work drains.
+// so only the new entries are read, which no solve touches yet (a submap's solve takes the list
+// length of its own keyframe's prefix); otherwise everything is recounted after the bundling work drains.
 void Recon::computePairBounds(bool append) {
     if (!append) {
-        baDrain();
         BF_HIP(hipStreamSynchronize(baStream_));
         pairSeen_.clear();
         pairCountedN_ = 0;
@@ -326,7 +290,6 @@ void Recon::setInitialPose(const BFMat4& T0) {
     kf_[0] = T0;
     kfSolved_[0] = 1;
     globalT_[0] = T0;
-    baDrain();
     BF_HIP(hipMemcpyAsync(dSeedT_.p, T0.m, 64, hipMemcpyHostToDevice, baStream_));
     matrices_to_poses(dSeedT_.p, 1, dGlobalRot_.p, dGlobalTrans_.p, dOne_.p, baStream_);
     BF_HIP(hipStreamSynchronize(baStream_));
@@ -573,21 +536,12 @@ void Recon::endSubmap(uint32_t s, uint32_t n) {
     const uint32_t base = s * S;
     if (inflight_.size() == RING) {  // ring full: wait for the oldest result
         Pending& old = ring_[inflight_.front()];
-        const auto tw = std::chrono::steady_clock::now();
-        baWaitFor(old.job);
-        BF_HIP(hipEventSynchronize(old.done));
-        st_.hostWaitMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
+        waitResult(old);
         apply(old);
         inflight_.pop_front();
     }
-    const uint32_t slot = ringNext_;
-    ringNext_ = (ringNext_ + 1) % RING;
+    const uint32_t slot = takeSlot(s, n, s + 1, false);
     Pending& P = ring_[slot];
-    P.submap = s;
-    P.numLocal = n;
-    P.localSolved = P.globalSolved = false;
-    P.endSolve = false;
-    P.issueFrame = numFrames_;
 
     // ---- local solve over frames base .. base+n-1 (first frame fixed) ----------------------
     bool haveCache = opt_.useLocalDense != 0;
@@ -600,75 +554,46 @@ void Recon::endSubmap(uint32_t s, uint32_t n) {
         P.cacheTable[i] = fr.cache;
         if (!fr.cache.depth) haveCache = false;
     }
-    const uint32_t nk = s + 1;
-    BF_REQUIRE(nk + 1 <= opt_.maxKeyframes, BF_ERR_CAPACITY, "keyframes exceed maxKeyframes");
-    switchBundlingPriority(nk);
-    P.numKeyframes = nk;
-    const std::pair<BFEntryJ*, uint32_t> lc = localCorr_[s];
-    // everything below only issues work on baStream_ from state fixed at this point: the bundling
-    // thread runs it while the frame loop goes on enqueuing scene work
-    const hipEvent_t cev = cacheEv_;  // the submap's last cache store (the frame thread re-points cacheEv_)
-    // the global list as of this frame: the frame thread may append keyframes' correspondences (the app)
-    // while a bundling thread issues this submap, so the issue works from these values, not the members
-    GlobalView gv{globalCorr_, globalCorrN_, (s < globalPrefix_.size()) ? globalPrefix_[s] : globalCorrN_,
-                  (comm_ && s < pairBound_.size()) ? std::max(pairBound_[s], 1u) : 0u};
-    baPost([this, s, n, S, slot, haveCache, lc, nk, cev, gv]() { issueSubmap(s, n, S, slot, haveCache, lc, nk, cev, gv); });
-    P.job = lastJob_;
+    BF_REQUIRE(P.numKeyframes + 1 <= opt_.maxKeyframes, BF_ERR_CAPACITY, "keyframes exceed maxKeyframes");
+    issueSubmap(P, haveCache);
     inflight_.push_back(slot);
     lastSubmapEnqueued_ = s;
     // m_totalNumOptLocalFrames (OnlineBundler.cpp:268): the frames the complete trajectory covers
     optimizedFrames_ = S * s + std::min(n, S);
 }
 
-// Round 5: with the voxel pass in four resident rounds (a slot frees every ~120 us instead of once per pass),
-// the bundling streams run at normal priority by default: the bench stream 1 446-1 458 (high) -> 1 470-1 474
-// frames/s, the G = 8 rehearsal 3 707-3 732 -> 3 812-3 825 (profiles/r10_ba_priority_ab.txt). The keyed
-// policy below (BF_BA_HIGH_PRIORITY=keyed) was round 4's, measured with one resident round:
-// Bundling streams at the highest queue priority take CU slots ahead of the scene stream's next workgroups
-// (priority orders dispatch; it never preempts a running workgroup):
-// - sharded, each GPU has a fraction of the voxel work and the (replicated) bundling is co-critical: +7 % at
-//   G = 4, +11 % at G = 8 (one rank's share on one GPU, profiles/r3n_late_experiments.txt);
-// - unsharded, while the global solve's persistent grid (about N / 4 workgroups of the 512 slots at 2 per
-//   CU) leaves the scene stream a quarter of the device: the bench stream (K = 500) 1 300 -> 1 362-1 367
-//   frames/s, config 5's stream (K = 1 000) 181.6 -> 183.7. At normal priority each of a solve's dependent
-//   launches waits for slots behind the voxel pass, the submap's result misses its hand-off frame and the
-//   frame loop blocks with less work queued (profiles/r8u_*, r8v_*, r9b_*);
-// - solves above kHighPriorityMaxKeyframes keyframes (config 4's 2 000), whose grid needs nearly every
-//   slot, starve the scene stream at high priority instead (981 -> 921 frames/s): they run at normal priority.
-// Keyed on the solve being issued (nk keyframes), not on the run's capacity: a run sized for 2 000
-// keyframes bundles at high priority until its solves pass the bound. The switch (once per run: K only
-// grows) orders the new streams after the old ones' work and moves both solvers onto them.
-void Recon::switchBundlingPriority(uint32_t nk) {
-    if (priorityPolicy_ >= 0) return;  // fixed by BF_BA_HIGH_PRIORITY
-    const bool high = sharded_ || nk <= kHighPriorityMaxKeyframes;
-    if (high == baHigh_) return;
-    hipStream_t ba = high ? baStreamHi_ : baStreamLo_, loc = high ? localStreamHi_ : localStreamLo_;
-    if (!ba || !loc) return;  // that priority was not created for this run
-    baDrain();                // a bundling thread has issued everything queued on the old streams
-    hipEvent_t e[2];
-    for (hipEvent_t& x : e) BF_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-    BF_HIP(hipEventRecord(e[0], baStream_));
-    BF_HIP(hipEventRecord(e[1], localStream_));
-    for (hipStream_t st : {ba, loc})
-        for (hipEvent_t x : e) BF_HIP(hipStreamWaitEvent(st, x, 0));
-    for (hipEvent_t x : e) BF_HIP(hipEventDestroy(x));
-    baStream_ = ba;
-    localStream_ = loc;
-    global_->setStream(ba);
-    local_->setStream(loc);
-    baHigh_ = high;
+uint32_t Recon::takeSlot(uint32_t submap, uint32_t numLocal, uint32_t numKeyframes, bool endSolve) {
+    const uint32_t slot = ringNext_;
+    ringNext_ = (ringNext_ + 1) % RING;
+    Pending& P = ring_[slot];
+    P.submap = submap;
+    P.numLocal = numLocal;
+    P.numKeyframes = numKeyframes;
+    P.localSolved = P.globalSolved = false;
+    P.endSolve = endSolve;
+    P.issueFrame = numFrames_;
+    return slot;
 }
 
-void Recon::issueSubmap(uint32_t s, uint32_t n, uint32_t S, uint32_t slot, bool haveCache,
-                        std::pair<BFEntryJ*, uint32_t> lc, uint32_t nk, hipEvent_t cev, GlobalView gv) {
-    Pending& P = ring_[slot];
+void Recon::waitResult(Pending& P) {
+    const auto tw = std::chrono::steady_clock::now();
+    BF_HIP(hipEventSynchronize(P.done));
+    st_.hostWaitMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
+}
+
+// Enqueues submap P.submap's solves from the loop's state as of this frame: its local correspondences, the last
+// cache store (cacheEv_) and the global list, of which the global solve takes the prefix of the submap's own
+// keyframe (keyframes' correspondences appended later, by the app, belong to later submaps' solves).
+void Recon::issueSubmap(Pending& P, bool haveCache) {
+    const uint32_t S = opt_.submapSize, s = P.submap, n = P.numLocal, nk = P.numKeyframes;
+    const std::pair<BFEntryJ*, uint32_t> lc = localCorr_[s];
     const uint32_t L = S + 1;
     const int bi = (int)(s & 1u);
     LocalSet& B = ls_[bi];
     // ---- local solve over frames base .. base+n-1 (first frame fixed), on the local stream ----------
     // set bi was last read by global solve s - 2
     BF_HIP(hipStreamWaitEvent(localStream_, globalDone_[bi], 0));
-    if (cev) BF_HIP(hipStreamWaitEvent(localStream_, cev, 0));  // the submap's cache frames
+    if (cacheEv_) BF_HIP(hipStreamWaitEvent(localStream_, cacheEv_, 0));  // the submap's cache frames
     BF_HIP(hipMemcpyAsync(B.T.p, P.localInit, 64 * n, hipMemcpyHostToDevice, localStream_));
     matrices_to_poses(B.T.p, n, B.rot.p, B.trans, B.valid.p, localStream_);
     // multi-GPU: submap s's local solve runs on rank s % R only (the submaps are independent units,
@@ -744,30 +669,20 @@ void Recon::issueSubmap(uint32_t s, uint32_t n, uint32_t S, uint32_t slot, bool 
     // 399-405). Keyframe 0 is never invalidated (the reference exits on an invalid first chunk,
     // Bundler.cpp:377-384).
     const int* gate = (verify && s > 0) ? B.gate : nullptr;
-    if (gate && gv.corr) invalidate_local(gate, s, dGlobalValid_.p, gv.corr, gv.n, baStream_);
-    const uint32_t ncorr = gv.ncorr;
-    if (nk >= 2 && gv.corr && ncorr > 0) {
+    if (gate && globalCorr_) invalidate_local(gate, s, dGlobalValid_.p, globalCorr_, globalCorrN_, baStream_);
+    const uint32_t ncorr = (s < globalPrefix_.size()) ? globalPrefix_[s] : globalCorrN_;
+    const bool solve = nk >= 2 && globalCorr_ && ncorr > 0;
+    if (solve) {
         std::vector<float> ws(opt_.globalNonLin, 1.0f), wz(opt_.globalNonLin, 0.0f);  // SBA.cpp:34-39, dense off
-        SolveArgs a{};
-        a.corr = gv.corr;
-        a.numCorr = ncorr;
-        a.valid = dGlobalValid_.p;
-        a.numImages = nk;
-        a.nNonLin = opt_.globalNonLin;
-        a.nLin = opt_.globalLin;
+        SolveArgs a = globalSolveArgs(nk, ncorr);
         a.wSparse = ws.data();
         a.wDenseDepth = wz.data();
         a.wDenseColor = wz.data();
-        a.rot = dGlobalRot_.p;
-        a.trans = dGlobalTrans_.p;
-        a.rebuildJT = true;
-        a.findMaxResidual = true;
         a.gate = gate;
-        if (gv.pairBound) a.pairBound = gv.pairBound;
         const bool capture = s == capSubmap_;
         if (capture) {  // test hook: the solve's inputs, as it sees them (after invalidate_local)
             const size_t K = opt_.maxKeyframes;
-            BF_HIP(hipMemcpyAsync(capCorrIn_.p, gv.corr, sizeof(BFEntryJ) * ncorr, hipMemcpyDeviceToDevice, baStream_));
+            BF_HIP(hipMemcpyAsync(capCorrIn_.p, globalCorr_, sizeof(BFEntryJ) * ncorr, hipMemcpyDeviceToDevice, baStream_));
             BF_HIP(hipMemcpyAsync(capPoseIn_.p, dGlobalRot_.p, 12 * (size_t)nk, hipMemcpyDeviceToDevice, baStream_));
             BF_HIP(hipMemcpyAsync(capPoseIn_.p + 3 * K, dGlobalTrans_.p, 12 * (size_t)nk, hipMemcpyDeviceToDevice, baStream_));
             BF_HIP(hipMemcpyAsync(capValid_.p, dGlobalValid_.p, 4 * (size_t)nk, hipMemcpyDeviceToDevice, baStream_));
@@ -775,21 +690,15 @@ void Recon::issueSubmap(uint32_t s, uint32_t n, uint32_t S, uint32_t slot, bool 
         global_->solve(a);
         if (capture) {  // ... and its outcome, before the max-residual removal
             const size_t K = opt_.maxKeyframes;
-            BF_HIP(hipMemcpyAsync(capCorrOut_.p, gv.corr, sizeof(BFEntryJ) * ncorr, hipMemcpyDeviceToDevice, baStream_));
+            BF_HIP(hipMemcpyAsync(capCorrOut_.p, globalCorr_, sizeof(BFEntryJ) * ncorr, hipMemcpyDeviceToDevice, baStream_));
             BF_HIP(hipMemcpyAsync(capPoseOut_.p, dGlobalRot_.p, 12 * (size_t)nk, hipMemcpyDeviceToDevice, baStream_));
             BF_HIP(hipMemcpyAsync(capPoseOut_.p + 3 * K, dGlobalTrans_.p, 12 * (size_t)nk, hipMemcpyDeviceToDevice, baStream_));
             capN_ = ncorr;
             capK_ = nk;
             capDone_ = true;
         }
-        // removeMaxResidualCUDA with getMaxResidual's (0, <10) exemption, on the device
-        global_->removeMaxResidualAsync(gv.corr, ncorr, dGlobalValid_.p, nk, opt_.maxResidualThresh);
-        global_->resultAsync(P.ctrl + Solver::kResultWords);
-        P.globalSolved = true;
     }
-    poses_to_matrices(dGlobalRot_.p, dGlobalTrans_.p, nk, dGlobalT_.p, dGlobalValid_.p, baStream_);
-    BF_HIP(hipMemcpyAsync(P.globalT, dGlobalT_.p, 64 * nk, hipMemcpyDeviceToHost, baStream_));
-    BF_HIP(hipMemcpyAsync(P.valid, dGlobalValid_.p, 4 * nk, hipMemcpyDeviceToHost, baStream_));
+    globalSolveTail(P, solve ? ncorr : 0);
     BF_HIP(hipMemcpyAsync(P.gate, B.gate, 4, hipMemcpyDeviceToHost, baStream_));
     // ---- initNextGlobalTransformCU (OnlineBundler.cu:112-140): keyframe s+1 from the last local
     if (n == S + 1) seed_keyframe(B.rot.p, B.trans, S, dGlobalRot_.p, dGlobalTrans_.p, s, baStream_, gate);
@@ -797,12 +706,9 @@ void Recon::issueSubmap(uint32_t s, uint32_t n, uint32_t S, uint32_t slot, bool 
     BF_HIP(hipEventRecord(P.done, baStream_));
 }
 
-// One end-of-sequence global solve (OnlineBundler.cpp:171-197 + optimizeGlobal with isSequenceDone,
-// :373-398): every keyframe and correspondence, max-residual removal, optionally the dense depth term
-// of USE_GLOBAL_DENSE_AT_END (:177-189) over the keyframes' cache frames.
-void Recon::issueEndSolve(uint32_t slot, uint32_t nk, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1) {
-    Pending& P = ring_[slot];
-    std::vector<float> ws(opt_.globalNonLin, 1.0f), wd(opt_.globalNonLin, wDense), wc(opt_.globalNonLin, 0.0f);
+// what every global solve over keyframes 0..nk-1 and the first ncorr entries of the global list has in common
+// (the callers add the weights, and the gate or the dense term's cache)
+SolveArgs Recon::globalSolveArgs(uint32_t nk, uint32_t ncorr) const {
     SolveArgs a{};
     a.corr = globalCorr_;
     a.numCorr = ncorr;
@@ -810,6 +716,34 @@ void Recon::issueEndSolve(uint32_t slot, uint32_t nk, uint32_t ncorr, float wDen
     a.numImages = nk;
     a.nNonLin = opt_.globalNonLin;
     a.nLin = opt_.globalLin;
+    a.rot = dGlobalRot_.p;
+    a.trans = dGlobalTrans_.p;
+    a.rebuildJT = true;
+    a.findMaxResidual = true;
+    if (comm_ && nk - 1 < pairBound_.size()) a.pairBound = std::max(pairBound_[nk - 1], 1u);
+    return a;
+}
+
+// after P's global solve over ncorr entries (0: none ran): removeMaxResidualCUDA with getMaxResidual's (0, <10)
+// exemption, on the device, and the solver's result words; then the keyframe poses and validity for the host
+void Recon::globalSolveTail(Pending& P, uint32_t ncorr) {
+    const uint32_t nk = P.numKeyframes;
+    if (ncorr > 0) {
+        global_->removeMaxResidualAsync(globalCorr_, ncorr, dGlobalValid_.p, nk, opt_.maxResidualThresh);
+        global_->resultAsync(P.ctrl + Solver::kResultWords);
+        P.globalSolved = true;
+    }
+    poses_to_matrices(dGlobalRot_.p, dGlobalTrans_.p, nk, dGlobalT_.p, dGlobalValid_.p, baStream_);
+    BF_HIP(hipMemcpyAsync(P.globalT, dGlobalT_.p, 64 * nk, hipMemcpyDeviceToHost, baStream_));
+    BF_HIP(hipMemcpyAsync(P.valid, dGlobalValid_.p, 4 * nk, hipMemcpyDeviceToHost, baStream_));
+}
+
+// One end-of-sequence global solve (OnlineBundler.cpp:171-197 + optimizeGlobal with isSequenceDone,
+// :373-398): every keyframe and correspondence, max-residual removal, optionally the dense depth term
+// of USE_GLOBAL_DENSE_AT_END (:177-189) over the keyframes' cache frames.
+void Recon::issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1) {
+    std::vector<float> ws(opt_.globalNonLin, 1.0f), wd(opt_.globalNonLin, wDense), wc(opt_.globalNonLin, 0.0f);
+    SolveArgs a = globalSolveArgs(P.numKeyframes, ncorr);
     a.wSparse = ws.data();
     a.wDenseDepth = wd.data();
     a.wDenseColor = wc.data();
@@ -817,22 +751,11 @@ void Recon::issueEndSolve(uint32_t slot, uint32_t nk, uint32_t ncorr, float wDen
     a.cacheW = opt_.cacheWidth;
     a.cacheH = opt_.cacheHeight;
     std::memcpy(a.intrinsics, opt_.cacheIntrinsics, sizeof(a.intrinsics));
-    a.rot = dGlobalRot_.p;
-    a.trans = dGlobalTrans_.p;
-    a.rebuildJT = true;
-    a.findMaxResidual = true;
     if (cacheEv_ && wDense > 0.0f) BF_HIP(hipStreamWaitEvent(baStream_, cacheEv_, 0));
-    const uint32_t last = nk - 1;
-    if (comm_ && last < pairBound_.size()) a.pairBound = std::max(pairBound_[last], 1u);
     BF_HIP(hipEventRecord(t0, baStream_));
     global_->solve(a);
     BF_HIP(hipEventRecord(t1, baStream_));
-    global_->removeMaxResidualAsync(globalCorr_, ncorr, dGlobalValid_.p, nk, opt_.maxResidualThresh);
-    global_->resultAsync(P.ctrl + Solver::kResultWords);
-    P.globalSolved = true;
-    poses_to_matrices(dGlobalRot_.p, dGlobalTrans_.p, nk, dGlobalT_.p, dGlobalValid_.p, baStream_);
-    BF_HIP(hipMemcpyAsync(P.globalT, dGlobalT_.p, 64 * nk, hipMemcpyDeviceToHost, baStream_));
-    BF_HIP(hipMemcpyAsync(P.valid, dGlobalValid_.p, 4 * nk, hipMemcpyDeviceToHost, baStream_));
+    globalSolveTail(P, ncorr);
     BF_HIP(hipEventRecord(P.done, baStream_));
 }
 
@@ -862,22 +785,13 @@ SolveResult Recon::endSolve(float wDense, float* ms) {
         BF_HIP(hipMemcpyAsync(dGlobalCache_.p, tab.data(), sizeof(BFCachedFrame) * nk, hipMemcpyHostToDevice, baStream_));
         BF_HIP(hipStreamSynchronize(baStream_));
     }
-    const uint32_t slot = ringNext_;
-    ringNext_ = (ringNext_ + 1) % RING;
-    Pending& P = ring_[slot];
-    P.submap = last;
-    P.numLocal = 0;
-    P.numKeyframes = nk;
-    P.localSolved = P.globalSolved = false;
-    P.endSolve = true;
+    Pending& P = ring_[takeSlot(last, 0, nk, true)];
     *P.gate = 1;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     BF_HIP(hipEventCreate(&t0));
     BF_HIP(hipEventCreate(&t1));
     try {
-        baPost([this, slot, nk, ncorr, wDense, t0, t1]() { issueEndSolve(slot, nk, ncorr, wDense, t0, t1); });
-        P.job = lastJob_;
-        baWaitFor(P.job);
+        issueEndSolve(P, ncorr, wDense, t0, t1);
         BF_HIP(hipEventSynchronize(P.done));
         if (ms) BF_HIP(hipEventElapsedTime(ms, t0, t1));
     } catch (...) {
@@ -905,81 +819,14 @@ void Recon::submapPoses(uint32_t s, float* local, float* global, int32_t* valid,
     if (localValid) *localValid = r.localOk;
 }
 
-void Recon::baPost(std::function<void()> job) {
-    ++lastJob_;
-    if (!baThreaded_) {
-        job();
-        baDone_.store(lastJob_, std::memory_order_release);
-        return;
-    }
-    {
-        std::lock_guard<std::mutex> lk(baMu_);
-        baJobs_.push_back(std::move(job));
-    }
-    baCv_.notify_one();
-}
-
-void Recon::baLoop() {
-    for (;;) {
-        std::function<void()> job;
-        {
-            std::unique_lock<std::mutex> lk(baMu_);
-            baCv_.wait(lk, [this] { return baStop_ || !baJobs_.empty(); });
-            if (baJobs_.empty()) return;  // stop requested and nothing left
-            job = std::move(baJobs_.front());
-            baJobs_.pop_front();
-        }
-        try {
-            job();
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(baMu_);
-            if (!baErr_) baErr_ = std::current_exception();
-        }
-        {
-            std::lock_guard<std::mutex> lk(baMu_);
-            baDone_.fetch_add(1, std::memory_order_release);
-        }
-        baDoneCv_.notify_all();
-    }
-}
-
-void Recon::baWaitFor(uint64_t job) {
-    if (baDone_.load(std::memory_order_acquire) < job) {
-        std::unique_lock<std::mutex> lk(baMu_);
-        baDoneCv_.wait(lk, [this, job] { return baDone_.load(std::memory_order_acquire) >= job; });
-    }
-    std::exception_ptr e;
-    {
-        std::lock_guard<std::mutex> lk(baMu_);
-        e = baErr_;
-        baErr_ = nullptr;
-    }
-    if (e) std::rethrow_exception(e);
-}
-
-void Recon::baDrain() { baWaitFor(lastJob_); }
-
 void Recon::applyPending(bool block) {
-    if (!block && opt_.asyncBundling && opt_.resultLag) {
-        // repeatable hand-off: submap results are applied exactly resultLag frames after their issue
-        while (!inflight_.empty()) {
-            Pending& P = ring_[inflight_.front()];
-            if (numFrames_ < P.issueFrame + opt_.resultLag) break;
-            const auto tw = std::chrono::steady_clock::now();
-            baWaitFor(P.job);
-            BF_HIP(hipEventSynchronize(P.done));
-            st_.hostWaitMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-            apply(P);
-            inflight_.pop_front();
-        }
-        return;
-    }
+    // repeatable hand-off: submap results are applied exactly resultLag frames after their issue
+    const bool lagged = !block && opt_.asyncBundling && opt_.resultLag;
     while (!inflight_.empty()) {
         Pending& P = ring_[inflight_.front()];
-        if (!block && baDone_.load(std::memory_order_acquire) < P.job) break;  // not issued yet
-        baWaitFor(P.job);
-        if (block) {
-            BF_HIP(hipEventSynchronize(P.done));
+        if (lagged && numFrames_ < P.issueFrame + opt_.resultLag) break;
+        if (block || lagged) {
+            waitResult(P);
         } else {
             const hipError_t q = hipEventQuery(P.done);
             if (q == hipErrorNotReady) break;
@@ -1068,7 +915,6 @@ void Recon::apply(Pending& P) {
 
 void Recon::synchronize() {
     flushIntegrate();
-    baDrain();
     BF_HIP(hipStreamSynchronize(sceneStream_));
     BF_HIP(hipStreamSynchronize(localStream_));
     BF_HIP(hipStreamSynchronize(baStream_));

@@ -17,16 +17,12 @@
 //      keyframe pose — from the solver when its result has arrived, else dead-reckoned
 // In async mode the TSDF never waits for the solver, as the reference's reconstruction thread
 // never waits for its bundling thread; in sync mode step 1 waits, which makes runs repeatable.
+// One host thread drives all of it: the solves are enqueued from the frame loop onto two bundling
+// streams of their own (baStream_, localStream_), at the scene stream's priority.
 #pragma once
 #include <array>
-#include <atomic>
-#include <condition_variable>
 #include <deque>
-#include <exception>
-#include <functional>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <unordered_set>
 #include <vector>
 
@@ -101,7 +97,6 @@ private:
     struct Pending {  // one submap's bundling results in flight
         uint32_t submap = 0, numLocal = 0, numKeyframes = 0;
         uint32_t issueFrame = 0;    // the frame whose processing issued it (resultLag)
-        uint64_t job = 0;  // bundling-thread job that enqueues this submap's work (see baPost)
         bool localSolved = false, globalSolved = false;
         bool endSolve = false;      // an end-of-sequence global solve (no local part)
         hipEvent_t done = nullptr;
@@ -114,13 +109,12 @@ private:
         BFCachedFrame* cacheTable = nullptr; // pinned staging [S+1] (H2D of the local cache table)
     };
     void endSubmap(uint32_t s, uint32_t numFrames);
-    struct GlobalView {  // the global correspondence list as a submap's issue sees it
-        BFEntryJ* corr;
-        uint32_t n, ncorr, pairBound;
-    };
-    void issueSubmap(uint32_t s, uint32_t n, uint32_t S, uint32_t slot, bool haveCache, std::pair<BFEntryJ*, uint32_t> lc,
-                     uint32_t nk, hipEvent_t cacheEv, GlobalView gv);
-    void issueEndSolve(uint32_t slot, uint32_t nk, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1);
+    uint32_t takeSlot(uint32_t submap, uint32_t numLocal, uint32_t numKeyframes, bool endSolve);  // the next ring slot
+    void issueSubmap(Pending& P, bool haveCache);
+    void issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1);
+    SolveArgs globalSolveArgs(uint32_t nk, uint32_t ncorr) const;
+    void globalSolveTail(Pending& P, uint32_t ncorr);
+    void waitResult(Pending& P);  // until P's solves are done; the wait counts as hostWaitMs
     void applyPending(bool block);
     void apply(Pending& p);
     void runReintegrate();
@@ -143,16 +137,9 @@ private:
     BFDepthCameraParams cam_;
     // baStream_: global solves (and the multi-GPU exchanges, in one order on every rank); localStream_:
     // local solves, which depend only on their submap's frames, so submap s+1's local solve runs while
-    // submap s's global solve is still in flight
+    // submap s's global solve is still in flight. All three at normal queue priority
     hipStream_t sceneStream_ = nullptr, baStream_ = nullptr, localStream_ = nullptr;
     hipStream_t copyStream_ = nullptr;  // host readbacks of inputs (computePairBounds), created on first use
-    // bundling streams at the highest and at normal queue priority; baStream_ / localStream_ are the active
-    // pair (switchBundlingPriority, keyed on the size of the solve being issued)
-    hipStream_t baStreamHi_ = nullptr, baStreamLo_ = nullptr, localStreamHi_ = nullptr, localStreamLo_ = nullptr;
-    static constexpr uint32_t kHighPriorityMaxKeyframes = 1537;  // persistent grid <= ~3/4 of the CU slots
-    bool baHigh_ = true, sharded_ = false;
-    int priorityPolicy_ = -1;  // -1: by solve size; 0 / 1: normal / high throughout (BFReconOptions.bundlingPriority)
-    void switchBundlingPriority(uint32_t nk);
     std::unique_ptr<Scene> scene_;
     std::unique_ptr<Solver> local_, global_;
     std::unique_ptr<TrajectoryManager> tm_;
@@ -214,25 +201,6 @@ private:
     std::vector<Pending> ring_;
     std::deque<uint32_t> inflight_;     // ring indices in submap order
     uint32_t ringNext_ = 0;
-
-    // Bundling thread (the reference's bundling thread, OnlineBundler), asyncBundling = 2: a submap's
-    // local + global solves are ~450 kernel launches; the frame loop posts them as one job and this
-    // thread issues them on baStream_ in post order, so the loop never spends the launch time. Off by
-    // default (jobs run inline): without a profiler the host issues them faster than the scene stream
-    // drains its queue, and the bench showed no difference (949 vs 949 frames/s).
-    void baPost(std::function<void()> job);  // returns the job's sequence number in lastJob_
-    void baWaitFor(uint64_t job);            // until job `job` has been issued (rethrows its error)
-    void baDrain();                          // until every posted job has been issued
-    void baLoop();
-    bool baThreaded_ = true;
-    std::thread baThread_;
-    std::mutex baMu_;
-    std::condition_variable baCv_, baDoneCv_;
-    std::deque<std::function<void()>> baJobs_;
-    bool baStop_ = false;
-    uint64_t lastJob_ = 0;           // jobs posted (frame-loop thread)
-    std::atomic<uint64_t> baDone_{0};  // jobs issued
-    std::exception_ptr baErr_;
 
     // per-submap local state, double-buffered by submap parity: set s & 1 is written by local solve s
     // and read by global solve s (gate, keyframe seed); local solve s + 2 waits for globalDone_[s & 1]

@@ -125,7 +125,6 @@ public:
 
     const SceneConfig& config() const { return cfg_; }
     hipStream_t stream() const { return stream_; }
-    void setStream(hipStream_t s) { stream_ = s; }
     // raw device views for the raycaster / stream runner
     const BFHashEntry* dHash() const { return hash_.p; }
     const BFVoxel* dVoxels() const { return voxels_.p; }

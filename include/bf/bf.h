@@ -335,7 +335,8 @@ typedef struct BFReconOptions {
     int32_t asyncBundling;       /* 1: solves run on their own stream and their poses are picked up
                                     by the frame loop when ready (the reference's bundling thread);
                                     0: the loop waits for each submap's solves (deterministic);
-                                    2: as 1, with the solves issued from a separate host thread */
+                                    2: accepted and exactly 1 (it once issued the solves from a separate host
+                                    thread, which gained nothing; the loop is single-threaded) */
     BFSolverOptions solver;
     int32_t disableLocalVerify;  /* 0: s_useLocalVerify = true (zParametersBundlingDefault.txt:62): after each local
                                     solve useVerification + VerifyTrajectoryCU; a failing submap is invalidated
@@ -346,10 +347,8 @@ typedef struct BFReconOptions {
                                     L > 0 = they are applied exactly L frames after the submap was issued
                                     (waiting for them if needed), so the run's op sequence is repeatable;
                                     L <= 8 * submapSize (the result ring), else BF_ERR_ARG */
-    int32_t bundlingPriority;    /* v4. queue priority of the bundling streams: 0 normal, as the scene stream (default:
-                                    the voxel pass runs in resident rounds, so a bundling launch finds slots within a
-                                    round); 1 the highest; 2 keyed on the solve being issued (highest up to 1 537
-                                    keyframes or when sharded, normal above: the round-4 policy) */
+    int32_t bundlingPriority;    /* v4. reserved, must be 0 (else BF_ERR_ARG): the bundling streams run at normal queue
+                                    priority, as the scene stream */
 } BFReconOptions;
 
 typedef struct BFReconStats {
@@ -372,7 +371,7 @@ typedef struct BFReconStats {
     uint64_t pcgRecoveries;      /* solves whose persistent PCG timed out and was redone (BF_SOLVE_PCG_RECOVERED);
                                     a solve with a BF_SOLVE_ERR_FATAL bit fails the call with BF_ERR_INTERNAL */
     double hostMs;               /* host wall time inside bf_recon_process_frame (enqueueing + waits) */
-    double hostWaitMs;           /* ... of it blocked on bundling results (resultLag, a full ring) */
+    double hostWaitMs;           /* ... of it blocked on bundling results (resultLag, a full ring, asyncBundling 0) */
     uint64_t globalPcgLaunches;  /* timed persistent PCG launches of the global solves (one per GN step) */
     double globalPcgKernelMs;    /* their summed device time (dispatch-stamped events) */
     uint64_t renders;            /* v4: per-frame renders (bf_recon_set_render) */
@@ -1042,7 +1041,7 @@ typedef struct BFAppOptions {
     int32_t overwriteSens;      /* 1: the trajectory goes into the input .sens (the reference overwrites it);
                                    0: into <outputDir>/<stem>.optimized.sens */
     int32_t skipOutputs;        /* 1: no .sens / .ply / processed.txt */
-    int32_t asyncBundling;      /* BFReconOptions.asyncBundling (the app default is 1) */
+    int32_t asyncBundling;      /* BFReconOptions.asyncBundling (the app default is 1; 2 is accepted and exactly 1) */
     int32_t recordOps;          /* BFReconOptions.recordOps (tests) */
     int32_t enableTiming;       /* BFReconOptions.enableTiming */
     uint32_t maxFrames;         /* read at most this many frames (0: all; CUDAImageManager also stops at

@@ -143,3 +143,9 @@ def test_option_checks_without_device():
         h = C.c_void_p()
         assert L.bf_scene_create(C.byref(p), C.byref(so), C.byref(h)) != 0
         assert msg in L.bf_last_error()
+    cam = bfa.depth_camera(80, 60, fx=577.87 / 8, fy=577.87 / 8)
+    for value in (1, 2, -1):  # reserved: the bundling streams run at normal priority
+        ro = abi.BFReconOptions(maxFrames=4, bundlingPriority=value)
+        h = C.c_void_p()
+        assert L.bf_recon_create(C.byref(p), None, C.byref(cam), C.byref(ro), C.byref(h)) == -2  # BF_ERR_ARG
+        assert b"bundlingPriority" in L.bf_last_error()
