@@ -278,6 +278,12 @@ class BFBundlerRetry(C.Structure):  # what the last fuse_submap / retry did abou
         ("seeds", (C.c_uint32 * 2) * 5), ("reserved", C.c_uint32)]
 
 
+class BFReconBundling(C.Structure):  # include/bf/types.h: what the loop did with an attached bundler
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "framesNotIntegrated", "submapsFused", "submapsInvalidEarly",
+                                          "submapsInvalidVerified", "keyframesLost", "keyframesCleared")] + [
+        ("bundlerMs", C.c_double)]
+
+
 BUNDLER_NO_FRAME, BUNDLER_LOCAL, BUNDLER_OPT_LOCAL, BUNDLER_GLOBAL = 0xFFFFFFFF, 0, 1, 2
 SIFT_LEVELS, SIFT_MAX_FILTER, SIFT_TRUNCATED = 12, 33, 1
 SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("depth", "<f4")])
@@ -287,6 +293,7 @@ assert C.sizeof(BFMatchVerifyOptions) == 32
 assert C.sizeof(BFSiftOptions) == 48
 assert C.sizeof(BFBundlerFrame) == 168
 assert C.sizeof(BFBundlerRetry) == 80
+assert C.sizeof(BFReconBundling) == 64
 
 
 class BFVoxelOp(C.Structure):  # include/bf/bf.h

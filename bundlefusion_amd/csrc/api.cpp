@@ -212,7 +212,8 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFBundlerSubmap", sizeof(BFBundlerSubmap)},
         {"BFBundlerKeyframe", sizeof(BFBundlerKeyframe)},
         {"BFBundlerStats", sizeof(BFBundlerStats)},
-        {"BFBundlerRetry", sizeof(BFBundlerRetry)}};
+        {"BFBundlerRetry", sizeof(BFBundlerRetry)},
+        {"BFReconBundling", sizeof(BFReconBundling)}};
     for (const auto& e : kSizes)
         if (std::strcmp(e.n, name) == 0) {
             *out = e.s;
@@ -752,7 +753,9 @@ int bf_comm_allreduce_sum_f64(bf_comm* c, double* d, size_t n) {
 // ---- reconstruction loop ----------------------------------------------------------------
 struct bf_recon {
     Recon* r = nullptr;
+    bf_bundler* bundler = nullptr;  // attached (borrowed): its borrowed stage handles follow the swaps the loop causes
 };
+static void bundler_refresh(bf_bundler* h);
 
 int bf_recon_create(const BFHashParams* params, const BFSceneOptions* sceneOpts, const BFDepthCameraParams* cam,
                     const BFReconOptions* opts, bf_recon** out) {
@@ -805,6 +808,12 @@ int bf_recon_set_initial_pose(bf_recon* r, const float T0[16]) {
 int bf_recon_process_frame(bf_recon* r, uint32_t f) {
     BF_TRY
     BF_REQUIRE(r, BF_ERR_ARG, "null recon");
+    struct Refresh {  // also when the frame fails: the bundler may have swapped its local sets by then
+        bf_bundler* h;
+        ~Refresh() {
+            if (h) bundler_refresh(h);
+        }
+    } refresh{r->bundler};
     r->r->processFrame(f);
     BF_CATCH
 }
@@ -1714,6 +1723,34 @@ int bf_retry_debug_close(bf_bundler* b, uint32_t idx, BFBundlerRetry* out) {
     BF_TRY
     BF_REQUIRE(b && out, BF_ERR_ARG, "null argument");
     b->b->debugRetryClose(idx, out);
+    BF_CATCH
+}
+
+// ---- the pose-free loop: a bundler attached to the reconstruction loop ------------------------------------
+int bf_recon_attach_bundler(bf_recon* r, bf_bundler* b) {
+    BF_TRY
+    BF_REQUIRE(r && b, BF_ERR_ARG, "null argument");
+    r->r->attachBundler(b->b);
+    r->bundler = b;
+    BF_CATCH
+}
+int bf_recon_set_frame_bundling(bf_recon* r, uint32_t f, const uint8_t* d_color, uint32_t colorW, uint32_t colorH,
+                                const float* d_depthFilt, const float* d_depthRaw) {
+    BF_TRY
+    BF_REQUIRE(r && d_color && d_depthFilt && d_depthRaw, BF_ERR_ARG, "null argument");
+    r->r->setFrameBundling(f, d_color, colorW, colorH, d_depthFilt, d_depthRaw);
+    BF_CATCH
+}
+int bf_recon_bundler_frame(bf_recon* r, uint32_t f, BFBundlerFrame* out) {
+    BF_TRY
+    BF_REQUIRE(r && out, BF_ERR_ARG, "null argument");
+    r->r->bundlerFrame(f, out);
+    BF_CATCH
+}
+int bf_recon_bundling_stats(bf_recon* r, BFReconBundling* out) {
+    BF_TRY
+    BF_REQUIRE(r && out, BF_ERR_ARG, "null argument");
+    *out = r->r->bundlingStats();
     BF_CATCH
 }
 

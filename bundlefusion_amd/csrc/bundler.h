@@ -90,6 +90,8 @@ public:
     Cache& cache(uint32_t which) { return which == BF_BUNDLER_GLOBAL ? *cacheGlob_ : *cacheLoc_[which == BF_BUNDLER_LOCAL ? cur_ : 1 - cur_]; }
     const float* intensity() const { return lastIntensity_; }
     const BFBundlerStats& stats() const { return stats_; }
+    uint32_t numFrames() const { return frame_; }      // frames processed since create / reset
+    bool retryEnabled() const { return retry_; }
 
 private:
     // one launch of k_frame_close for image `cur` of matcher m on list `list` (0 / 1 local, 2 global), then the wait

@@ -73,6 +73,14 @@ T* pinned(size_t n) {
 }
 }  // namespace
 
+// host wall time of a scope, added to a counter (BFReconBundling.bundlerMs)
+struct Recon::HostMsTimer {
+    double& ms;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    explicit HostMsTimer(double& acc) : ms(acc) {}
+    ~HostMsTimer() { ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+};
+
 Recon::Recon(const BFHashParams& hp, const BFSceneOptions* so, const BFDepthCameraParams& cam, const BFReconOptions& o)
     : opt_(o), cam_(cam) {
     opt_.submapSize = or_default(o.submapSize, 10u);
@@ -196,6 +204,7 @@ Recon::~Recon() {
                         (void*)p.cacheTable, (void*)p.gate})
             if (q) (void)hipHostFree(q);
     }
+    if (completeStage_) (void)hipHostFree(completeStage_);
     scene_.reset();
     local_.reset();
     global_.reset();
@@ -247,6 +256,7 @@ void Recon::setGlobalCorrespondences(BFEntryJ* corr, uint32_t n, const uint32_t*
 
 void Recon::setComm(Comm* c) {
     BF_REQUIRE(numFrames_ == 0, BF_ERR_STATE, "set the communicator before the first frame");
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the pose-free loop is not sharded");
     comm_ = c;
     global_->setShard(c ? (uint32_t)c->size() : 1u, c ? (uint32_t)c->rank() : 0u, c);
     if (comm_ && globalCorr_) computePairBounds(false);
@@ -287,6 +297,8 @@ void Recon::computePairBounds(bool append) {
 }
 
 void Recon::setInitialPose(const BFMat4& T0) {
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: its trajectory starts at the identity");
+    initialPoseSet_ = true;
     kf_[0] = T0;
     kfSolved_[0] = 1;
     globalT_[0] = T0;
@@ -476,11 +488,14 @@ void Recon::processFrame(uint32_t f) {
         applyPending(false);
     }
     FrameRef& fr = frames_[f];
+    // processInput before process() (OnlineBundler.cpp:167-227, 410-416): the frame's integration transform comes from
+    // the complete trajectory as it stood before the submap this frame closes was solved
+    if (bundler_) bundleFrame(f);
     if (f % S == 0 && f > 0) {
         BF_HOST_T(HS_SUBMAP);
         endSubmap(s - 1, S + 1);
         if (!opt_.asyncBundling) applyPending(true);
-        if (!kfSolved_[s]) {  // solver result not back yet: dead-reckon the new keyframe
+        if (!kfSolved_[s] && !bundler_) {  // solver result not back yet: dead-reckon the new keyframe
             BF_REQUIRE(s < kf_.size(), BF_ERR_CAPACITY, "keyframes exceed maxKeyframes");
             kf_[s] = mat4_mul(kf_[s - 1], mat4_mul(frames_[f - 1].Tlocal, fr.Tinc));
         }
@@ -493,14 +508,27 @@ void Recon::processFrame(uint32_t f) {
         scene_->raycast(renderT, cam_, renderParams_, rDepth_.p, rDepth4_.p, rNormals_.p, rColors_.p, nullptr, nullptr);
         st_.renders++;
     }
-    fr.Tlocal = (f % S == 0) ? identity() : mat4_mul(frames_[f - 1].Tlocal, fr.Tinc);
-    const BFMat4 T = mat4_mul(kf_[s], fr.Tlocal);  // getCurrentIntegrationFrame
-    pendingOp_ = frameOp(f, T, false);
-    pendingInt_ = true;
-    logOp(2, f, &T);
-    st_.integrations++;
-    tm_->addFrame(FrameType::Integrated, T, f);
-    traceQueue(0, f, 1, &T, nullptr);
+    if (bundler_ && !bundlerFrames_[f].valid) {
+        // no transform for this frame (getCurrentIntegrationFrame false): DepthSensing.cpp:1029-1053
+        const BFMat4 none = ninf_mat();
+        tm_->addFrame(FrameType::NotIntegrated_NoTransform, none, f);
+        traceQueue(0, f, 1, &none, nullptr);
+        bst_.framesNotIntegrated++;
+    } else {
+        BFMat4 T;
+        if (bundler_) {  // getCurrentIntegrationFrame (OnlineBundler.cpp:229-240): computeSiftTransformCU's three cases
+            std::memcpy(T.m, bundlerFrames_[f].integrateTransform, 64);
+        } else {
+            fr.Tlocal = (f % S == 0) ? identity() : mat4_mul(frames_[f - 1].Tlocal, fr.Tinc);
+            T = mat4_mul(kf_[s], fr.Tlocal);  // getCurrentIntegrationFrame
+        }
+        pendingOp_ = frameOp(f, T, false);
+        pendingInt_ = true;
+        logOp(2, f, &T);
+        st_.integrations++;
+        tm_->addFrame(FrameType::Integrated, T, f);
+        traceQueue(0, f, 1, &T, nullptr);
+    }
     numFrames_++;
     st_.frames++;
     st_.hostMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tStart).count();
@@ -525,7 +553,8 @@ void Recon::finish() {
     const uint32_t s = (numFrames_ - 1) / S, n = numFrames_ - s * S;
     // a last submap of one frame is only the previous submap's overlap frame, solved with it
     // (isLastLocalFrame skips prepareLocalSolve for it, OnlineBundler.cpp:170-172, OnlineBundler.h:42)
-    if (s != lastSubmapEnqueued_ && n >= 2) endSubmap(s, n);
+    // with a bundler the trailing partial submap stays at its integration poses (the end-of-sequence phase is not attached)
+    if (s != lastSubmapEnqueued_ && n >= 2 && !bundler_) endSubmap(s, n);
     synchronize();
 }
 
@@ -545,7 +574,8 @@ void Recon::endSubmap(uint32_t s, uint32_t n) {
 
     // ---- local solve over frames base .. base+n-1 (first frame fixed) ----------------------
     bool haveCache = opt_.useLocalDense != 0;
-    for (uint32_t i = 0; i < n; i++) {
+    if (bundler_) bundleSubmapInputs(P);
+    for (uint32_t i = 0; i < n && !bundler_; i++) {
         const FrameRef& fr = frames_[base + i];
         BF_REQUIRE(fr.set, BF_ERR_STATE, "local solve over a frame not in the frame store");
         // the submap's last local frame is the next submap's first: chain it from frame S-1
@@ -590,11 +620,23 @@ void Recon::issueSubmap(Pending& P, bool haveCache) {
     const uint32_t L = S + 1;
     const int bi = (int)(s & 1u);
     LocalSet& B = ls_[bi];
+    // attached bundler: its closed submap (endSubmap took the list and the cache table from it). The closing frame left
+    // copies in flight on the bundler's stream (the valid flags, the overlap frame): the host waits for them here
+    BFBundlerSubmap sm{};
+    bool earlyInvalid = false;  // Bundler::isValid false: prepareLocalSolve's INVALIDATE (OnlineBundler.cpp:147-158)
+    if (bundler_) {
+        HostMsTimer t(bst_.bundlerMs);
+        bundler_->submap(&sm);
+        earlyInvalid = sm.isValid == 0;
+        BF_HIP(hipStreamSynchronize(bundler_->stream()));
+    }
     // ---- local solve over frames base .. base+n-1 (first frame fixed), on the local stream ----------
     // set bi was last read by global solve s - 2
     BF_HIP(hipStreamWaitEvent(localStream_, globalDone_[bi], 0));
     if (cacheEv_) BF_HIP(hipStreamWaitEvent(localStream_, cacheEv_, 0));  // the submap's cache frames
     BF_HIP(hipMemcpyAsync(B.T.p, P.localInit, 64 * n, hipMemcpyHostToDevice, localStream_));
+    // the images the bundler holds invalid are invalid for the solve (their initial rows are -inf and stay so)
+    if (bundler_) BF_HIP(hipMemcpyAsync(B.valid.p, sm.d_validImages, sizeof(int) * n, hipMemcpyDeviceToDevice, localStream_));
     matrices_to_poses(B.T.p, n, B.rot.p, B.trans, B.valid.p, localStream_);
     // multi-GPU: submap s's local solve runs on rank s % R only (the submaps are independent units,
     // SURVEY.md §8(e)2); its poses and verification outcome are then broadcast so that every rank
@@ -605,7 +647,7 @@ void Recon::issueSubmap(Pending& P, bool haveCache) {
     const bool solveHere = !shardLocal || localOwner == comm_->rank();
     const bool verify = opt_.disableLocalVerify == 0;
     const size_t bcast = 6 * (size_t)L + 1;  // [rot | trans | gate]
-    const bool haveLocal = n >= 2 && lc.first && lc.second > 0;
+    const bool haveLocal = n >= 2 && lc.first && lc.second > 0 && !earlyInvalid;
     if (haveLocal && solveHere) {
         if (haveCache)
             BF_HIP(hipMemcpyAsync(B.cache.p, P.cacheTable, sizeof(BFCachedFrame) * n, hipMemcpyHostToDevice, localStream_));
@@ -651,8 +693,18 @@ void Recon::issueSubmap(Pending& P, bool haveCache) {
         local_->resultAsync(P.ctrl);
         P.localSolved = true;
     } else if (!haveLocal) {
-        set_gate(B.gate, nullptr, localStream_);
+        set_gate(B.gate, earlyInvalid ? dZero_.p : nullptr, localStream_);
         std::memcpy(P.localT, P.localInit, 64 * n);
+    }
+    if (bundler_) {
+        // the host reads the gate, the bundler fuses (or invalidates) and matches the new key frame, and the loop takes
+        // its global list: all host-ordered, before the global part is enqueued
+        BF_HIP(hipMemcpyAsync(P.gate, B.gate, sizeof(int), hipMemcpyDeviceToHost, localStream_));
+        const auto tw = std::chrono::steady_clock::now();
+        BF_HIP(hipStreamSynchronize(localStream_));
+        st_.hostWaitMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
+        // global tracking lost: the gate machinery does the rest (invalid key frame, no global solve, frames to -inf)
+        if (!bundleGlobal(P, B, earlyInvalid)) set_gate(B.gate, dZero_.p, localStream_);
     }
     BF_HIP(hipEventRecord(localDone_[bi], localStream_));
     BF_HIP(hipStreamWaitEvent(baStream_, localDone_[bi], 0));
@@ -668,7 +720,8 @@ void Recon::issueSubmap(Pending& P, bool haveCache) {
     // global solve is skipped (processGlobal / optimizeGlobal INVALIDATE, OnlineBundler.cpp:351-360,
     // 399-405). Keyframe 0 is never invalidated (the reference exits on an invalid first chunk,
     // Bundler.cpp:377-384).
-    const int* gate = (verify && s > 0) ? B.gate : nullptr;
+    // With a bundler the gate always counts, for key frame 0 too: the bundler goes on after an invalid first submap.
+    const int* gate = (bundler_ || (verify && s > 0)) ? B.gate : nullptr;
     if (gate && globalCorr_) invalidate_local(gate, s, dGlobalValid_.p, globalCorr_, globalCorrN_, baStream_);
     const uint32_t ncorr = (s < globalPrefix_.size()) ? globalPrefix_[s] : globalCorrN_;
     const bool solve = nk >= 2 && globalCorr_ && ncorr > 0;
@@ -701,7 +754,10 @@ void Recon::issueSubmap(Pending& P, bool haveCache) {
     globalSolveTail(P, solve ? ncorr : 0);
     BF_HIP(hipMemcpyAsync(P.gate, B.gate, 4, hipMemcpyDeviceToHost, baStream_));
     // ---- initNextGlobalTransformCU (OnlineBundler.cu:112-140): keyframe s+1 from the last local
-    if (n == S + 1) seed_keyframe(B.rot.p, B.trans, S, dGlobalRot_.p, dGlobalTrans_.p, s, baStream_, gate);
+    uint32_t lastLocal = S;  // with a bundler the last VALID local frame (OnlineBundler.cpp:313-322)
+    if (bundler_)
+        for (lastLocal = n - 1; lastLocal > 0 && !submapValid_[s][lastLocal]; lastLocal--) {}
+    if (n == S + 1) seed_keyframe(B.rot.p, B.trans, lastLocal, dGlobalRot_.p, dGlobalTrans_.p, s, baStream_, gate);
     BF_HIP(hipEventRecord(globalDone_[bi], baStream_));
     BF_HIP(hipEventRecord(P.done, baStream_));
 }
@@ -760,6 +816,7 @@ void Recon::issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t
 }
 
 SolveResult Recon::endSolve(float wDense, float* ms) {
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the end-of-sequence phase is not part of the pose-free loop");
     synchronize();  // every submap result applied: the ring is empty
     const uint32_t S = opt_.submapSize;
     BF_REQUIRE(numFrames_ > 0, BF_ERR_STATE, "end solve before the first frame");
@@ -906,11 +963,15 @@ void Recon::apply(Pending& P) {
     HostPool::get().parallel_for(optimized, [this, S](size_t b, size_t e) {  // independent per frame
         for (size_t g = b; g < e; g++) {
             const size_t k = g / S;
-            complete_[g] = (globalValid_[k] && localKnown_[k]) ? mat4_mul(globalT_[k], localTraj_[k][g % S]) : ninf_mat();
+            // an image the bundler held invalid in its submap has a -inf local pose: its row is -inf, not a product
+            // with it (invalidateImages, OnlineBundler.cpp:317-320)
+            const bool ok = globalValid_[k] && localKnown_[k] && !(bundler_ && !submapValid_[k][g % S]);
+            complete_[g] = ok ? mat4_mul(globalT_[k], localTraj_[k][g % S]) : ninf_mat();
         }
     }, 1024);
     tm_->updateOptimizedTransforms(complete_.data(), optimized);
     traceQueue(1, 0, optimized, complete_.data(), nullptr);
+    if (bundler_) bundleTrajectory(P, optimized, localOk);
 }
 
 void Recon::synchronize() {
@@ -960,6 +1021,7 @@ void Recon::resetStats() {
 
 void Recon::attachCache(Cache* c) {
     BF_REQUIRE(numFrames_ == 0, BF_ERR_STATE, "attach the cache before the first frame");
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the local solves read its cache frames");
     BF_REQUIRE(!c || c->config().width == opt_.cacheWidth && c->config().height == opt_.cacheHeight, BF_ERR_ARG,
                "cache size differs from the loop's cacheWidth x cacheHeight");
     BF_REQUIRE(!c || !preproc_ || (preproc_->depthWidth() == c->config().inputWidth && preproc_->depthHeight() == c->config().inputHeight),
@@ -980,6 +1042,7 @@ void Recon::setFrameSource(uint32_t f, const float* depth, const uint8_t* color,
 
 void Recon::attachPreproc(Preproc* p) {
     BF_REQUIRE(numFrames_ == 0, BF_ERR_STATE, "attach the preprocessing before the first frame");
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: its caller preprocesses the frames");
     BF_REQUIRE(!p || (p->integrationWidth() == cam_.imageWidth && p->integrationHeight() == cam_.imageHeight), BF_ERR_ARG,
                "preprocessing output size differs from the integration size");
     // the cache reads the preprocessing's sensor-size raw depth (k_cache_geometry: inputWidth x inputHeight)
@@ -1052,6 +1115,7 @@ void Recon::storeCacheFrame(uint32_t f) {
 
 BFEndSequenceResult Recon::endSequence(const BFEndSequenceOptions& o) {
     BFEndSequenceResult res{};
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the end-of-sequence phase is not part of the pose-free loop");
     synchronize();
     if (numFrames_ == 0) return res;
     const int32_t N = o.numSolveFramesBeforeExit;
@@ -1135,6 +1199,147 @@ void Recon::traceQueue(int32_t kind, uint32_t frame, uint32_t count, const BFMat
         }
     }
     qEvents_.push_back(e);
+}
+
+// ---- attached bundler (the pose-free loop, synchronous form) -------------------------------------------------------
+void Recon::attachBundler(Bundler* b) {
+    BF_REQUIRE(b != nullptr, BF_ERR_ARG, "null bundler");
+    const BundlerConfig& c = b->config();
+    BF_REQUIRE(opt_.asyncBundling == 0, BF_ERR_ARG, "a bundler attaches to the synchronous loop only (asyncBundling 0)");
+    BF_REQUIRE(c.submapSize == opt_.submapSize && c.maxKeyframes == opt_.maxKeyframes, BF_ERR_ARG,
+               "the bundler's submapSize / maxKeyframes differ from the loop's");
+    const float* K = b->cache(BF_BUNDLER_LOCAL).intrinsics();  // at the cache size
+    BF_REQUIRE(c.cache.width == opt_.cacheWidth && c.cache.height == opt_.cacheHeight && K[0] == opt_.cacheIntrinsics[0] &&
+                   K[5] == opt_.cacheIntrinsics[1] && K[2] == opt_.cacheIntrinsics[2] && K[6] == opt_.cacheIntrinsics[3],
+               BF_ERR_ARG, "the bundler's cache size or intrinsics differ from the loop's cacheWidth / cacheHeight / cacheIntrinsics");
+    BF_REQUIRE(c.maxLocalCorr <= opt_.maxLocalCorr && c.maxGlobalCorr <= opt_.maxGlobalCorr, BF_ERR_ARG,
+               "the bundler's maxLocalCorr / maxGlobalCorr exceed the loop's");
+    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached already");
+    BF_REQUIRE(numFrames_ == 0 && b->numFrames() == 0, BF_ERR_STATE, "attach the bundler before the first frame");
+    BF_REQUIRE(!comm_ && !cache_ && !preproc_, BF_ERR_STATE, "a communicator, a cache or a preprocessor is attached");
+    BF_REQUIRE(!b->retryEnabled(), BF_ERR_STATE, "retry is enabled on the bundler");
+    BF_REQUIRE(!initialPoseSet_, BF_ERR_STATE, "an initial pose was set: the bundler's trajectory starts at the identity");
+    const size_t frames = (size_t)c.submapSize * c.maxKeyframes;
+    completeStage_ = pinned<float>(16 * frames);
+    dComplete_.alloc(16 * frames);
+    dZero_.alloc(1);
+    BF_HIP(hipMemsetAsync(dZero_.p, 0, sizeof(int), baStream_));
+    BF_HIP(hipStreamSynchronize(baStream_));
+    bundlingIn_.assign(opt_.maxFrames, BundlingRef{});
+    bundlerFrames_.clear();
+    bundlerFrames_.reserve(opt_.maxFrames);
+    submapValid_.assign(localCorr_.size(), {});
+    loopInvalid_.assign(opt_.maxKeyframes, 0);
+    bundler_ = b;
+}
+
+void Recon::setFrameBundling(uint32_t f, const uint8_t* color, uint32_t colorW, uint32_t colorH, const float* depthFilt,
+                             const float* depthRaw) {
+    BF_REQUIRE(bundler_, BF_ERR_STATE, "no bundler attached");
+    BF_REQUIRE(f < opt_.maxFrames, BF_ERR_CAPACITY, "frame index beyond maxFrames");
+    bundlingIn_[f] = BundlingRef{color, colorW, colorH, depthFilt, depthRaw};
+}
+
+void Recon::bundlerFrame(uint32_t f, BFBundlerFrame* out) const {
+    BF_REQUIRE(bundler_ && f < bundlerFrames_.size(), BF_ERR_ARG, "no bundler attached, or the frame has not been processed");
+    *out = bundlerFrames_[f];
+}
+
+// processInput (OnlineBundler.cpp:167-227) for frame f; returns with the frame's record in pinned memory read
+void Recon::bundleFrame(uint32_t f) {
+    const BundlingRef& in = bundlingIn_[f];
+    BF_REQUIRE(in.color && in.depthFilt && in.depthRaw, BF_ERR_STATE, "frame has no bundling images (bf_recon_set_frame_bundling)");
+    BFBundlerFrame rec{};
+    {
+        HostMsTimer t(bst_.bundlerMs);
+        bundler_->processFrame(in.color, in.colorW, in.colorH, in.depthFilt, in.depthRaw, &rec);
+    }
+    bundlerFrames_.push_back(rec);
+    bst_.frames++;
+}
+
+// The closed submap as the local solve takes it: the bundler's list and cache table, and the sift chain relative to
+// the submap's first frame as initial poses (rigid inverse and product in double, rounded once, as frontend.h). An
+// image the bundler holds invalid gets a -inf row; image 0 is the fixed identity.
+void Recon::bundleSubmapInputs(Pending& P) {
+    const uint32_t S = opt_.submapSize, s = P.submap, n = P.numLocal, base = s * S;
+    BFBundlerSubmap sm{};
+    bundler_->submap(&sm);
+    BF_REQUIRE(sm.submap == s && sm.numFrames == n && !sm.released, BF_ERR_INTERNAL, "the bundler's closed submap is not the loop's");
+    localCorr_[s] = {sm.d_corr, sm.numCorr};
+    submapValid_[s].assign(sm.validImages, sm.validImages + n);
+    const float* A = bundlerFrames_[base].siftPose;
+    double inv[16] = {0};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) inv[4 * i + j] = (double)A[4 * j + i];
+        inv[4 * i + 3] = -((double)A[4 * 0 + i] * A[3] + (double)A[4 * 1 + i] * A[7] + (double)A[4 * 2 + i] * A[11]);
+    }
+    inv[15] = 1.0;
+    for (uint32_t i = 0; i < n; i++) {
+        BFMat4 Tl = i == 0 ? identity() : ninf_mat();
+        if (i > 0 && sm.validImages[i]) {
+            const float* B = bundlerFrames_[base + i].siftPose;
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) {
+                    double acc = 0.0;
+                    for (int k = 0; k < 4; k++) acc += inv[4 * r + k] * (double)B[4 * k + c];
+                    Tl.m[4 * r + c] = (float)acc;
+                }
+        }
+        std::memcpy(P.localInit + 16 * i, Tl.m, 64);
+        P.cacheTable[i] = sm.cacheFrames[i];
+    }
+}
+
+// processGlobal (OnlineBundler.cpp:280-361) between the local and the global part, host-ordered: the local stream has
+// been waited for and P.gate read. Afterwards the bundler's stream is drained and the loop holds its global list.
+bool Recon::bundleGlobal(Pending& P, LocalSet& B, bool earlyInvalid) {
+    const uint32_t s = P.submap;
+    bool lost = false;
+    HostMsTimer t(bst_.bundlerMs);
+    if (*P.gate != 0) {
+        BFBundlerKeyframe kf{};
+        bundler_->fuseSubmap(B.T.p, &kf);
+        BF_REQUIRE(kf.keyframe == s, BF_ERR_INTERNAL, "the bundler's key frame is not the loop's");
+        bst_.submapsFused++;
+        if (s > 0 && kf.valid == 0) {  // global tracking lost (:333-336)
+            lost = true;
+            bst_.keyframesLost++;
+        }
+    } else {
+        bundler_->invalidSubmap();
+        if (earlyInvalid) bst_.submapsInvalidEarly++;
+        else bst_.submapsInvalidVerified++;
+    }
+    BFEntryJ* corr = nullptr;
+    const uint32_t* prefix = nullptr;
+    uint32_t n = 0, nk = 0;
+    bundler_->global(&corr, nullptr, &n, &prefix, &nk);
+    BF_REQUIRE(nk == s + 1, BF_ERR_INTERNAL, "the bundler's key frame count is not the loop's");
+    setGlobalCorrespondences(corr, n, prefix, nk);
+    BF_HIP(hipStreamSynchronize(bundler_->stream()));
+    loopInvalid_[s] = (*P.gate == 0 || lost) ? 1 : 0;
+    return !lost;
+}
+
+// After apply(P) gave the queue its transforms: the same rows to the bundler (OnlineBundler.cpp:394-397), and the valid
+// flags the global solve cleared to the bundler's global store (in the reference the two share that array)
+void Recon::bundleTrajectory(const Pending& P, uint32_t optimized, bool localOk) {
+    const uint32_t S = opt_.submapSize, s = P.submap, nk = P.numKeyframes;
+    HostMsTimer t(bst_.bundlerMs);
+    if (globalValid_[s] && localOk) lastValidComplete_ = S * s;
+    if (optimized > 0) {
+        std::memcpy(completeStage_, complete_.data(), 64 * (size_t)optimized);
+        BF_HIP(hipMemcpyAsync(dComplete_.p, completeStage_, 64 * (size_t)optimized, hipMemcpyHostToDevice, bundler_->stream()));
+        bundler_->setCompleteTrajectory(dComplete_.p, optimized, lastValidComplete_);
+    }
+    Matcher& G = bundler_->matcher(BF_BUNDLER_GLOBAL);
+    for (uint32_t k = 0; k < nk && k < G.numImages(); k++)
+        if (!globalValid_[k] && !loopInvalid_[k] && G.valid(k)) {
+            G.setValid(k, 0);
+            bst_.keyframesCleared++;
+        }
+    BF_HIP(hipStreamSynchronize(bundler_->stream()));
 }
 
 void Recon::trajectory(BFMat4* out, uint32_t n) const {

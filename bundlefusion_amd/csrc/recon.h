@@ -2,8 +2,9 @@
 // hierarchical (local submap -> global keyframe) bundle adjustment, i.e. the parts of
 // DepthSensing.cpp's frame loop (Source/DepthSensing/DepthSensing.cpp:1003-1056, reintegrate
 // :854-902) and OnlineBundler (Source/OnlineBundler.cpp:242-416, OnlineBundler.cu:6-140) that sit
-// on the north-star path. Correspondence *production* (SiftGPU) is out of scope: EntryJ lists
-// are inputs, as if the matcher had filled SIFTImageManager's global correspondence array.
+// on the north-star path. Without a bundler attached, correspondence *production* (SiftGPU) is outside:
+// EntryJ lists are inputs, as if the matcher had filled SIFTImageManager's global correspondence array.
+// With one attached (attachBundler, synchronous mode only) the loop drives it: frames in, scene out.
 //
 // Ordering per frame f (submap size S, s = f / S):
 //   0. pick up finished bundling results (async mode): poses -> trajectory -> TrajectoryManager
@@ -28,6 +29,7 @@
 
 #include "../../include/bf/bf.h"
 #include "ba.h"
+#include "bundler.h"
 #include "cache.h"
 #include "frames.h"
 #include "trajectory.h"
@@ -65,6 +67,13 @@ public:
     // frame-store slot when it is processed (the cache then reads the raw sensor depth and colour)
     void attachPreproc(Preproc* p);
     void setFrameRaw(uint32_t f, const uint16_t* depthU16, const uint8_t* rgbx);
+    // The pose-free loop (synchronous): b (borrowed) gives every frame's integration pose and every EntryJ list; each
+    // hand-off between its stream and the loop's streams is a host wait (bf_recon_attach_bundler)
+    void attachBundler(Bundler* b);
+    void setFrameBundling(uint32_t f, const uint8_t* color, uint32_t colorW, uint32_t colorH, const float* depthFilt,
+                          const float* depthRaw);
+    void bundlerFrame(uint32_t f, BFBundlerFrame* out) const;
+    const BFReconBundling& bundlingStats() const { return bst_; }
     // TrajectoryManager::getOptimizedTransforms (TrajectoryManager.h:50-68)
     uint32_t optimizedTrajectory(BFMat4* out, uint32_t cap) const;
     // recordOps: the TrajectoryManager call sequence (bf_recon_queue_trace)
@@ -244,6 +253,32 @@ private:
     void awaitPreproc(uint32_t f);               // the scene stream after frame f's preprocessing
     void storeCacheFrame(uint32_t f);
     void preprocessFrame(uint32_t f);
+
+    // ---- attached bundler ----
+    struct BundlingRef {  // frame f's bundling images (setFrameBundling)
+        const uint8_t* color = nullptr;
+        uint32_t colorW = 0, colorH = 0;
+        const float* depthFilt = nullptr;
+        const float* depthRaw = nullptr;
+    };
+    struct HostMsTimer;  // adds its lifetime to bst_.bundlerMs
+    Bundler* bundler_ = nullptr;
+    bool initialPoseSet_ = false;
+    std::vector<BundlingRef> bundlingIn_;
+    std::vector<BFBundlerFrame> bundlerFrames_;      // the record of every processed frame
+    std::vector<std::vector<int32_t>> submapValid_;  // per closed submap: the bundler's validImages (S + 1 flags)
+    std::vector<char> loopInvalid_;                  // key frame k was invalidated by the loop itself (gate 0)
+    uint32_t lastValidComplete_ = 0;                 // m_lastValidCompleteTransform
+    float* completeStage_ = nullptr;                 // pinned [submapSize * maxKeyframes][16]
+    DevBuf<float> dComplete_;                        // the upload setCompleteTrajectory copies from
+    DevBuf<int> dZero_;
+    BFReconBundling bst_{};
+    void bundleFrame(uint32_t f);                    // Bundler::processFrame on frame f's images -> bundlerFrames_[f]
+    void bundleSubmapInputs(Pending& P);             // Bundler::submap -> the local list, cache table and initial poses
+    // after the local part: fuse / invalid, the global list, the host waits. Returns false when the gate must be 0
+    // although the local solve passed (global tracking lost)
+    bool bundleGlobal(Pending& P, LocalSet& B, bool earlyInvalid);
+    void bundleTrajectory(const Pending& P, uint32_t optimized, bool localOk);  // setCompleteTrajectory + valid flags
 
     // recordOps: TrajectoryManager call trace
     std::vector<BFQueueEvent> qEvents_;

@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import check, lib
-from .abi import (ENTRYJ_DTYPE, BFEndSequenceOptions, BFEndSequenceResult, BFFixOp, BFQueueEvent, BFReconOptions, BFReconStats,
-                  BFSolveResult, BFTsdfStats)
+from .abi import (ENTRYJ_DTYPE, BFBundlerFrame, BFEndSequenceOptions, BFEndSequenceResult, BFFixOp, BFQueueEvent,
+                  BFReconBundling, BFReconOptions, BFReconStats, BFSolveResult, BFTsdfStats)
 
 FIX_DEINTEGRATE, FIX_INTEGRATE, FIX_REINTEGRATE, OP_GC = 1, 2, 3, 4
 
@@ -61,6 +61,16 @@ def pose_helper_matrix_to_pose(T) -> np.ndarray:
     out = (C.c_float * 6)()
     check(lib().bf_pose_helper_matrix_to_pose(_mat(T), out))
     return np.array(out[:], np.float32)
+
+
+def bundler_cache_intrinsics(bundler_opts) -> tuple:
+    """(fx, fy, mx, my) of a bundler's cache frames: BFBundlerOptions.cache.inputIntrinsics scaled to the cache size in
+    float32 as CUDACache::CUDACache scales them. What BFReconOptions.cacheIntrinsics must hold for attach_bundler."""
+    c = bundler_opts.cache
+    f = np.float32
+    K = [f(c.inputIntrinsics[k]) for k in (0, 5, 2, 6)]
+    return (float(K[0] * (f(c.width) / f(c.inputWidth))), float(K[1] * (f(c.height) / f(c.inputHeight))),
+            float(K[2] * (f(c.width - 1) / f(c.inputWidth - 1))), float(K[3] * (f(c.height - 1) / f(c.inputHeight - 1))))
 
 
 def recon_options(max_frames: int, **kw) -> BFReconOptions:
@@ -163,6 +173,31 @@ class Recon:
         """CUDAImageManager::process per processed frame (DepthSensing.cpp:986); pre: io.Preprocessor."""
         self._preproc = pre
         check(lib().bf_recon_attach_preproc(self.h, pre.h if pre is not None else None))
+
+    def attach_bundler(self, bundler):
+        """The pose-free loop (bf_recon_attach_bundler; bundler: bundler.Bundler, borrowed, it must outlive the loop):
+        every frame's integration pose and every EntryJ list then come from the bundler. Synchronous loop only."""
+        check(lib().bf_recon_attach_bundler(self.h, bundler.h if bundler is not None else None))
+        self._bundler = bundler
+
+    def set_frame_bundling(self, f: int, color, depth_filt, depth_raw=None):
+        """Frame f's bundling images as Bundler.process_frame takes them: color [h, w, 4] uint8 RGBX, depths float32
+        DeviceArrays at the detector's depth size (depth_raw None: the filtered image twice)."""
+        raw = depth_filt if depth_raw is None else depth_raw
+        check(lib().bf_recon_set_frame_bundling(self.h, C.c_uint32(f), color.ptr, C.c_uint32(color.shape[1]),
+                                                C.c_uint32(color.shape[0]), depth_filt.ptr, raw.ptr))
+
+    def bundler_frame(self, f: int) -> dict:
+        """The record the attached bundler returned for frame f (Bundler.process_frame's dict)."""
+        from .bundler import _frame_dict
+        r = BFBundlerFrame()
+        check(lib().bf_recon_bundler_frame(self.h, C.c_uint32(f), C.byref(r)))
+        return _frame_dict(r)
+
+    def bundling_stats(self) -> dict:
+        s = BFReconBundling()
+        check(lib().bf_recon_bundling_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in BFReconBundling._fields_}
 
     def set_frame_raw(self, f: int, depth_u16_ptr: int, rgbx_ptr: int):
         check(lib().bf_recon_set_frame_raw(self.h, C.c_uint32(f), C.c_void_p(depth_u16_ptr), C.c_void_p(rgbx_ptr)))

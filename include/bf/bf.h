@@ -925,6 +925,37 @@ int bf_retry_keyframe_frames(bf_bundler* b, uint32_t k, int32_t* valid, uint32_t
  * BF_ERR_STATE unless retry is on, no closed submap waits, 1 <= idx < numKeyframes - 1 and image idx is invalid. */
 int bf_retry_debug_close(bf_bundler* b, uint32_t idx, BFBundlerRetry* out);
 
+/* ---- the pose-free loop: a bundler attached to bf_recon_* (synchronous form). With a bundler attached the loop takes
+ * no pose and no correspondence from its caller: per frame it runs bf_bundler_process_frame on the frame's bundling
+ * images and integrates at the record's integrateTransform (getCurrentIntegrationFrame, OnlineBundler.cpp:229-240); at a
+ * submap boundary the bundler's list and cache table feed the local solve, the solved transforms go to
+ * bf_bundler_fuse_submap (or bf_bundler_invalid_submap), the bundler's global list feeds the global solve, and the
+ * complete trajectory goes back through bf_bundler_set_complete_trajectory. Every hand-off between the bundler's stream
+ * and the loop's is a host wait. Without a bundler every bf_recon_* call does what it did before.
+ *
+ * bf_recon_attach_bundler: b is BORROWED and must outlive the loop; the caller may read it (bf_bundler_global, _stats,
+ * the borrowed stages) and must not drive it. Before the first frame. BF_ERR_ARG: a null argument; asyncBundling != 0;
+ * submapSize or maxKeyframes differing between the two option sets; the bundler's cache size or its intrinsics at that
+ * size (inputIntrinsics scaled as CUDACache::CUDACache scales them) differing from BFReconOptions.cacheWidth / Height /
+ * cacheIntrinsics; the bundler's maxLocalCorr / maxGlobalCorr above the loop's. BF_ERR_STATE: a frame has been processed
+ * (by the loop or by the bundler); a communicator, a cache or a preprocessor is attached; retry is enabled on the
+ * bundler; bf_recon_set_initial_pose was called (the bundler's trajectory starts at the identity); a bundler is attached
+ * already. Once attached, bf_recon_set_comm, _attach_cache, _attach_preproc, _set_initial_pose, _end_solve and
+ * _end_sequence return BF_ERR_STATE, bf_recon_set_frame's Tinc and cache are ignored, and bf_recon_finish leaves a
+ * trailing partial submap at its integration poses. */
+int bf_recon_attach_bundler(bf_recon* r, bf_bundler* b);
+/* Frame f's three bundling images, as bf_bundler_process_frame takes them (copyToBundling's). They are read on the
+ * bundler's stream inside bf_recon_process_frame(f): complete when that call is made, valid until it returns (frame 0:
+ * until bf_recon_synchronize). bf_recon_set_frame is still needed for the integration images. BF_ERR_ARG: a null
+ * argument; BF_ERR_CAPACITY: f >= maxFrames; BF_ERR_STATE: no bundler attached. */
+int bf_recon_set_frame_bundling(bf_recon* r, uint32_t f, const uint8_t* d_color, uint32_t colorW, uint32_t colorH,
+                                const float* d_depthFilt, const float* d_depthRaw);
+/* The record the bundler returned for frame f (the loop keeps them). BF_ERR_ARG: a null argument, no bundler attached, or
+ * f not processed yet. */
+int bf_recon_bundler_frame(bf_recon* r, uint32_t f, BFBundlerFrame* out);
+/* BF_ERR_ARG: a null argument. All zero without a bundler. Waits for nothing. */
+int bf_recon_bundling_stats(bf_recon* r, BFReconBundling* out);
+
 /* test entry of the workgroup scan and ballot compaction that the compaction kernels share (csrc/wave.h): ONE workgroup
  * of wg lanes (256, 512 or 1024, else BF_ERR_ARG) walks d_in[n] in rounds of wg with a carry. flags == 0: d_out[i] =
  * d_in[0] + ... + d_in[i - 1] (uint32, wrapping), *d_total = the sum of all n. flags != 0: a word counts as 1 if it is

@@ -423,12 +423,25 @@ typedef struct BFBundlerStats {
     uint64_t keyframes;    /* images in the global store (fused or invalid) */
 } BFBundlerStats;
 
+/* What the loop did with an attached bundler (bf_recon_bundling_stats; all zero without one). */
+typedef struct BFReconBundling {
+    uint64_t frames;                  /* frames that went through bf_bundler_process_frame inside the loop */
+    uint64_t framesNotIntegrated;     /* of them reported valid == 0: NotIntegrated_NoTransform, no scene call */
+    uint64_t submapsFused;            /* closed submaps handed to fuse_submap (gate 1 after the local solve) */
+    uint64_t submapsInvalidEarly;     /* closed submaps with isValid == 0: no local solve ran (prepareLocalSolve's INVALIDATE) */
+    uint64_t submapsInvalidVerified;  /* closed submaps whose local solve ran and whose verification failed */
+    uint64_t keyframesLost;           /* fused key frames s > 0 that matched no earlier one (global tracking lost) */
+    uint64_t keyframesCleared;        /* key frames whose valid flag a global solve cleared, written back to the bundler */
+    double bundlerMs;                 /* host wall time inside the bundler's calls (process_frame, fuse, global, trajectory) */
+} BFReconBundling;
+
 #ifdef __cplusplus
 } /* extern "C" */
 
 static_assert(sizeof(BFSiftOptions) == 48, "BFSiftOptions is 48 B");
 static_assert(sizeof(BFBundlerFrame) == 168, "BFBundlerFrame is 168 B");
 static_assert(sizeof(BFBundlerRetry) == 80, "BFBundlerRetry is 80 B");
+static_assert(sizeof(BFReconBundling) == 64, "BFReconBundling is 64 B");
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
 static_assert(sizeof(BFMcTriangle) == 72, "MarchingCubesData::Triangle is 72 B");
