@@ -224,6 +224,12 @@ class SceneRepHashSDF:
         check(lib().bf_scene_get_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in BFTsdfStats._fields_}
 
+    def allocPretestStats(self) -> dict:
+        """The alloc walk's pre-test since the last resetStats, in tiles per integrate op (bf_scene_alloc_pretest_stats)."""
+        out = (C.c_uint64 * 2)()
+        check(lib().bf_scene_alloc_pretest_stats(self.h, out))
+        return {"skipped": out[0], "walked": out[1]}
+
     def resetStats(self):
         check(lib().bf_scene_reset_stats(self.h))
 

@@ -101,6 +101,7 @@ class BFSceneOptions(C.Structure):
 
 
 BF_SCENE_TEST_ALLOC_DIRECT = 1
+BF_SCENE_TEST_ALLOC_NO_PRETEST = 4
 
 
 class BFSceneCapacity(C.Structure):  # include/bf/types.h

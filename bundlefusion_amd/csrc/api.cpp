@@ -405,6 +405,12 @@ int bf_scene_get_stats(bf_scene* s, BFTsdfStats* out) {
     *out = s->scene->stats();
     BF_CATCH
 }
+int bf_scene_alloc_pretest_stats(bf_scene* s, uint64_t out[2]) {
+    BF_TRY
+    BF_REQUIRE(s && out, BF_ERR_ARG, "null argument");
+    s->scene->allocPretestStats(out);
+    BF_CATCH
+}
 int bf_scene_reset_stats(bf_scene* s) {
     BF_TRY
     BF_REQUIRE(s, BF_ERR_ARG, "null scene");
@@ -878,6 +884,13 @@ int bf_recon_scene_stats(bf_recon* r, BFTsdfStats* out) {
     BF_REQUIRE(r && out, BF_ERR_ARG, "null argument");
     r->r->synchronize();
     *out = r->r->scene().stats();
+    BF_CATCH
+}
+int bf_recon_alloc_pretest_stats(bf_recon* r, uint64_t out[2]) {
+    BF_TRY
+    BF_REQUIRE(r && out, BF_ERR_ARG, "null argument");
+    r->r->synchronize();
+    r->r->scene().allocPretestStats(out);
     BF_CATCH
 }
 int bf_recon_heap_free_count(bf_recon* r, uint32_t* count) {

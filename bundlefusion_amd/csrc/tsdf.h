@@ -49,6 +49,7 @@ struct SceneConfig {
     uint32_t shardIndex;
     float shardChunk;        // ownership chunk edge in metres (default 1 m, the streaming chunk)
     uint32_t allocForceDirect = 0;  // test switch (BF_SCENE_TEST_ALLOC_DIRECT): every walking tile also takes the alloc walk's congested path
+    uint32_t allocNoPretest = 0;    // test switch (BF_SCENE_TEST_ALLOC_NO_PRETEST): the alloc walk without its block-box pre-test
     uint32_t applyXcdRun = 0;       // voxel pass: work-list positions per XCD run (0: 64)
     uint32_t applyRounds = 0;       // voxel pass: rounds of resident workgroups (0: kApplyRounds)
     uint32_t splatRowCap = 0;       // test switch: ray-interval splat row-list capacity (0: 4 per heap block)
@@ -117,6 +118,8 @@ public:
     void enableErrorMirror();
     uint32_t mirroredErrorFlags() const { return errMirror_ ? __atomic_load_n(errMirror_, __ATOMIC_ACQUIRE) : 0u; }
     BFTsdfStats stats();
+    // alloc tiles since resetStats: {ended by the pre-test, went on into the walk}
+    void allocPretestStats(uint64_t out[2]);
     void resetStats();
     void exportState(BFHashEntry* hash, uint32_t* heap, uint32_t* heapCounter, BFVoxel* voxels);
     uint32_t exportVisible(int4* out, uint32_t cap);

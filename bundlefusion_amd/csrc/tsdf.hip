@@ -55,6 +55,7 @@ struct HashArgs {
     float rVoxelSize, rFx, rFy;
     uint32_t shardCount, shardIndex;
     uint32_t allocForceDirect;
+    uint32_t allocNoPretest;
     float shardChunk;
     // reference streaming bitmask (isSDFBlockStreamedOut, CUDASceneRepHashSDF.cu:152-163)
     const uint32_t* bitMask;
@@ -90,7 +91,10 @@ struct __attribute__((packed, aligned(4))) Vox3 {
 };
 
 enum StatField { S_PIXELS = 0, S_CAND, S_ALLOC, S_SCANNED, S_VISIBLE, S_VOXELS, S_GCBLOCKS, S_GCFREED, S_OVERFLOW, S_OPS,
-                 S_BAND, S_RMW, S_BOPS, S_BBLOCKS, S_BRMW, S_BUPD, S_BEVAL, S_BHALF };
+                 S_BAND, S_RMW, S_BOPS, S_BBLOCKS, S_BRMW, S_BUPD, S_BEVAL, S_BHALF,
+                 // past BFTsdfStats (Scene::allocPretestStats): alloc tiles the pre-test ended and tiles that went on
+                 // into the walk
+                 S_PRE_SKIP, S_PRE_WALK };
 constexpr int DEPTH_TILE = 8;    // 8x8-pixel depth-bound tiles for the band cull
 constexpr int DEPTH_TILE2 = 16;  // coarse level: 16x16 pixels
 constexpr int STAT_SLOTS = 64;
@@ -117,6 +121,17 @@ __device__ __forceinline__ int wave_sum(int v) {
     return (int)(__builtin_amdgcn_readlane(r, 0) + __builtin_amdgcn_readlane(r, 16) + __builtin_amdgcn_readlane(r, 32) +
                  __builtin_amdgcn_readlane(r, 48));
 }
+// Minimum / maximum over the 64 lanes of a fully active wave, same DPP steps as dpp_row_sum (~v reverses
+// the signed order, so the maximum is the minimum of the complements).
+__device__ __forceinline__ int wave_min(int v) {
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true));
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true));
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+__device__ __forceinline__ int wave_max(int v) { return ~wave_min(~v); }
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
     // 16-bit limbs: every partial sum of 64 lanes stays below 2^22, so no carries are lost
     unsigned long long s = 0;
@@ -426,47 +441,65 @@ struct RayWalk {  // one pixel's DDA state (CUDASceneRepHashSDF.cu:196-230)
     f3 tMax, tDelta, step;
     bool active;
 };
-__device__ __forceinline__ RayWalk ray_walk_setup(const HashArgs& A, const float* __restrict__ depthImg,
-                                                  const BFDepthCameraParams& cam, const BFMat4& T, uint32_t x, uint32_t y) {
-    RayWalk r;
-    r.active = x < cam.imageWidth && y < cam.imageHeight;
-    const float d = r.active ? depthImg[y * cam.imageWidth + x] : 0.0f;
-    if (d == -INFINITY || d == 0.0f) r.active = false;
-    if (d >= A.maxIntegrationDistance) r.active = false;
+// The walk's setup in two parts. The first gives the ray's end points and their blocks: all a tile
+// needs to bound the blocks its rays can visit (alloc_collect's pre-test). The second derives the DDA
+// state from them. Together they are the one sequence of float operations the setup always was.
+struct RayEnds {
+    f3 rayMin, rayMax;
+    i3 id, idEnd;  // blocks of rayMin / rayMax
+    bool active;
+};
+__device__ __forceinline__ RayEnds ray_walk_ends(const HashArgs& A, const float* __restrict__ depthImg,
+                                                 const BFDepthCameraParams& cam, const BFMat4& T, uint32_t x, uint32_t y) {
+    RayEnds e;
+    e.active = x < cam.imageWidth && y < cam.imageHeight;
+    const float d = e.active ? depthImg[y * cam.imageWidth + x] : 0.0f;
+    if (d == -INFINITY || d == 0.0f) e.active = false;
+    if (d >= A.maxIntegrationDistance) e.active = false;
     const float t = A.truncation + A.truncScale * d;
     const float minDepth = fminf(A.maxIntegrationDistance, d - t);
     const float maxDepth = fminf(A.maxIntegrationDistance, d + t);
-    if (minDepth >= maxDepth) r.active = false;
+    if (minDepth >= maxDepth) e.active = false;
+    e.rayMin = e.rayMax = mk3(0, 0, 0);
+    e.id = e.idEnd = {0, 0, 0};
+    if (e.active) {
+        // depth_to_camera's two divisions by fx / fy and world_to_block's six by the voxel size go through
+        // div_by_uniform (bit-identical in the ranges checked below; otherwise the IEEE form, per wave)
+        if (A.rFx != 0.0f) {  // launch-uniform
+            const float cx = div_by_uniform((float)x - cam.mx, cam.fx, A.rFx), cy = div_by_uniform((float)y - cam.my, cam.fy, A.rFy);
+            e.rayMin = xform(T, mk3(minDepth * cx, minDepth * cy, minDepth));
+            e.rayMax = xform(T, mk3(maxDepth * cx, maxDepth * cy, maxDepth));
+        } else {
+            e.rayMin = xform(T, depth_to_camera(cam, x, y, minDepth));
+            e.rayMax = xform(T, depth_to_camera(cam, x, y, maxDepth));
+        }
+        e.id = world_to_block_rcp(e.rayMin, A.voxelSize, A.rVoxelSize);
+        e.idEnd = world_to_block_rcp(e.rayMax, A.voxelSize, A.rVoxelSize);
+        const float big = fmaxf(fmaxf(fmaxf(fabsf(e.rayMin.x), fabsf(e.rayMin.y)), fmaxf(fabsf(e.rayMin.z), fabsf(e.rayMax.x))),
+                                fmaxf(fabsf(e.rayMax.y), fabsf(e.rayMax.z)));
+        const bool exactNeeded = A.rVoxelSize == 0.0f || big > 0x1p100f;
+        if (__builtin_amdgcn_ballot_w64(exactNeeded)) {
+            asm volatile("" ::: "memory");
+            if (exactNeeded) {
+                e.id = world_to_block(e.rayMin, A.voxelSize);
+                e.idEnd = world_to_block(e.rayMax, A.voxelSize);
+            }
+        }
+    }
+    return e;
+}
+__device__ __forceinline__ RayWalk ray_walk_from_ends(const HashArgs& A, const RayEnds& e) {
+    RayWalk r;
+    r.active = e.active;
     r.id = {0, 0, 0};
     r.idBound = {0, 0, 0};
     r.tMax = mk3(0, 0, 0);
     r.tDelta = mk3(0, 0, 0);
     r.step = mk3(0, 0, 0);
     if (r.active) {
-        // depth_to_camera's two divisions by fx / fy and world_to_block's six by the voxel size go through
-        // div_by_uniform (bit-identical in the ranges checked below; otherwise the IEEE form, per wave)
-        f3 rayMin, rayMax;
-        i3 idEnd;
-        if (A.rFx != 0.0f) {  // launch-uniform
-            const float cx = div_by_uniform((float)x - cam.mx, cam.fx, A.rFx), cy = div_by_uniform((float)y - cam.my, cam.fy, A.rFy);
-            rayMin = xform(T, mk3(minDepth * cx, minDepth * cy, minDepth));
-            rayMax = xform(T, mk3(maxDepth * cx, maxDepth * cy, maxDepth));
-        } else {
-            rayMin = xform(T, depth_to_camera(cam, x, y, minDepth));
-            rayMax = xform(T, depth_to_camera(cam, x, y, maxDepth));
-        }
-        r.id = world_to_block_rcp(rayMin, A.voxelSize, A.rVoxelSize);
-        idEnd = world_to_block_rcp(rayMax, A.voxelSize, A.rVoxelSize);
-        const float big = fmaxf(fmaxf(fmaxf(fabsf(rayMin.x), fabsf(rayMin.y)), fmaxf(fabsf(rayMin.z), fabsf(rayMax.x))),
-                                fmaxf(fabsf(rayMax.y), fabsf(rayMax.z)));
-        const bool exactNeeded = A.rVoxelSize == 0.0f || big > 0x1p100f;
-        if (__builtin_amdgcn_ballot_w64(exactNeeded)) {
-            asm volatile("" ::: "memory");
-            if (exactNeeded) {
-                r.id = world_to_block(rayMin, A.voxelSize);
-                idEnd = world_to_block(rayMax, A.voxelSize);
-            }
-        }
+        const f3 rayMin = e.rayMin, rayMax = e.rayMax;
+        const i3 idEnd = e.idEnd;
+        r.id = e.id;
         const f3 rayDir = normalize3(rayMax - rayMin);
         r.step = mk3((float)sgn(rayDir.x), (float)sgn(rayDir.y), (float)sgn(rayDir.z));
         const f3 bp = block_to_world(r.id.x + f2i(fmaxf(0.0f, fminf(r.step.x, 1.0f))), r.id.y + f2i(fmaxf(0.0f, fminf(r.step.y, 1.0f))),
@@ -489,6 +522,10 @@ __device__ __forceinline__ RayWalk ray_walk_setup(const HashArgs& A, const float
         if (A.shardCount > 1) r.active = segment_may_own(A, r.id, idEnd);
     }
     return r;
+}
+__device__ __forceinline__ RayWalk ray_walk_setup(const HashArgs& A, const float* __restrict__ depthImg,
+                                                  const BFDepthCameraParams& cam, const BFMat4& T, uint32_t x, uint32_t y) {
+    return ray_walk_from_ends(A, ray_walk_ends(A, depthImg, cam, T, x, y));
 }
 __device__ __forceinline__ void ray_walk_advance(RayWalk& r) {  // traverse (CUDASceneRepHashSDF.cu:231-246)
     if (r.tMax.x < r.tMax.y && r.tMax.x < r.tMax.z) {
@@ -537,6 +574,7 @@ __device__ __forceinline__ unsigned long long alloc_walk_direct(const HashArgs& 
     return emitted;
 }
 constexpr int ALLOC_OVF = 256;  // per tile: keys the congested LDS set could not place, tested in phase 2
+constexpr int ALLOC_BOX_MAX = 256;  // pre-test: most blocks in a tile's box (one lookup per thread)
 __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __restrict__ depthImg,
                                               const BFDepthCameraParams& cam, const BFMat4& T, const BFMat4& Tinv,
                                               unsigned long long* __restrict__ cand, uint32_t candCap,
@@ -545,9 +583,74 @@ __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __
     __shared__ uint32_t s_novf;
     const uint32_t x = blockIdx.x * ALLOC_TILE + (threadIdx.x % ALLOC_TILE);
     const uint32_t y = blockIdx.y * ALLOC_TILE + (threadIdx.x / ALLOC_TILE);
-    RayWalk r = ray_walk_setup(A, depthImg, cam, T, x, y);
-    // a tile none of whose rays walks (no valid depth, or, sharded, no ray near an owned chunk) ends here
-    if (!__syncthreads_or(r.active ? 1 : 0)) return;
+    const RayEnds e = ray_walk_ends(A, depthImg, cam, T, x, y);
+    unsigned long long* const tileStat =
+        A.stats + (size_t)(((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) % STAT_SLOTS) * STAT_FIELDS;
+    // The pre-test: a tile all of whose reachable blocks exist cannot emit a candidate (alloc_wants asks
+    // for absence), so it ends before the DDA. Reachable: every block a ray's DDA visits lies in the box
+    // spanned by the ray's first block `id` and the block `idEnd` of its far end, per axis. The axis'
+    // step has the sign of rayMax - rayMin, and world_to_block is monotone in the coordinate, so idEnd
+    // lies on the step's side of id (or the step is 0 and the coordinate never moves); the coordinate
+    // moves by one step at a time and the ray stops walking the moment it reaches idEnd + step, so while
+    // the ray is active the coordinate stays between id and idEnd (tests/test_alloc_box.py holds this
+    // against the oracle's walk). The tile's box is the union of its active rays' boxes; when it has at
+    // most ALLOC_BOX_MAX blocks, each thread looks one of them up. The box is a superset of the visited
+    // blocks: an absent block in it only means the tile goes on as before. At the bench workload 80 % of
+    // the tiles with a ray end here, 11 % have a larger box and 9 % an absent block; a limit of 512 in
+    // two rounds ends 86 % and the launch is no shorter for it (profiles/alloc_pretest_ab.txt).
+    if (!A.allocNoPretest) {
+        __shared__ int s_box[4][6];
+        int lox = INT_MAX, loy = INT_MAX, loz = INT_MAX, hix = INT_MIN, hiy = INT_MIN, hiz = INT_MIN;
+        if (e.active) {
+            lox = min(e.id.x, e.idEnd.x); hix = max(e.id.x, e.idEnd.x);
+            loy = min(e.id.y, e.idEnd.y); hiy = max(e.id.y, e.idEnd.y);
+            loz = min(e.id.z, e.idEnd.z); hiz = max(e.id.z, e.idEnd.z);
+        }
+        lox = wave_min(lox); loy = wave_min(loy); loz = wave_min(loz);
+        hix = wave_max(hix); hiy = wave_max(hiy); hiz = wave_max(hiz);
+        if ((threadIdx.x & 63u) == 0) {
+            int* b = s_box[threadIdx.x >> 6];
+            b[0] = lox; b[1] = loy; b[2] = loz; b[3] = hix; b[4] = hiy; b[5] = hiz;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            lox = min(lox, s_box[w][0]); loy = min(loy, s_box[w][1]); loz = min(loz, s_box[w][2]);
+            hix = max(hix, s_box[w][3]); hiy = max(hiy, s_box[w][4]); hiz = max(hiz, s_box[w][5]);
+        }
+        // a tile with no active ray (no valid depth) ends here: its box is empty
+        if (lox > hix) return;
+        const uint32_t dx = (uint32_t)hix - (uint32_t)lox, dy = (uint32_t)hiy - (uint32_t)loy, dz = (uint32_t)hiz - (uint32_t)loz;
+        const bool small = dx < (uint32_t)ALLOC_BOX_MAX && dy < (uint32_t)ALLOC_BOX_MAX && dz < (uint32_t)ALLOC_BOX_MAX &&
+                           (dx + 1u) * (dy + 1u) * (dz + 1u) <= (uint32_t)ALLOC_BOX_MAX;
+        if (small) {
+            // thread t takes block (t mod nx, (t / nx) mod ny, t / (nx ny)) of the box. t and the extents are at
+            // most ALLOC_BOX_MAX <= 1024, so (t + 0.5) * rcp(n) is farther from an integer (>= 1 / 2048) than its
+            // error (< 2e-4: rcp and the product round to 1.5 ulp of at most 1024)
+            static_assert(ALLOC_BOX_MAX <= 1024, "the float quotients below");
+            const uint32_t nx = dx + 1u, ny = dy + 1u, n = nx * ny * (dz + 1u);
+            const float rnx = __builtin_amdgcn_rcpf((float)nx), rny = __builtin_amdgcn_rcpf((float)ny);
+            bool absent = false;
+            for (uint32_t t = threadIdx.x; t < n; t += 256u) {
+                const uint32_t q = (uint32_t)(((float)t + 0.5f) * rnx);
+                const uint32_t qz = (uint32_t)(((float)q + 0.5f) * rny);
+                const int bx = lox + (int)(t - q * nx), by = loy + (int)(q - qz * ny), bz = loz + (int)qz;
+                // sharded: another rank's block cannot be emitted here either, whether it exists or not
+                absent |= owned(A, bx, by, bz) && lookup_ptr(A, bx, by, bz) == BF_FREE_ENTRY;
+            }
+            if (!__syncthreads_or(absent ? 1 : 0)) {
+                if (threadIdx.x == 0) atomicAdd(&tileStat[S_PRE_SKIP], 1ull);
+                return;
+            }
+        }
+        if (threadIdx.x == 0) atomicAdd(&tileStat[S_PRE_WALK], 1ull);
+    } else {
+        if (!__syncthreads_or(e.active ? 1 : 0)) return;
+        if (threadIdx.x == 0) atomicAdd(&tileStat[S_PRE_WALK], 1ull);
+    }
+    RayWalk r = ray_walk_from_ends(A, e);
+    // sharded: a tile none of whose rays comes near an owned chunk ends here
+    if (A.shardCount > 1 && !__syncthreads_or(r.active ? 1 : 0)) return;
     for (int k = threadIdx.x; k < LDS_SET; k += blockDim.x) set[k] = EMPTY_KEY;
     if (threadIdx.x == 0) s_novf = 0;
     __syncthreads();
@@ -657,6 +760,7 @@ __device__ __forceinline__ void alloc_collect(const HashArgs& A, const float* __
 // the global dedup of k_alloc_insert removes blocks several ops want)
 // waves per SIMD asked of the compiler for the batched walk: 8 (63 VGPRs, 78 SGPRs with 65 spilled to VGPR lanes)
 // against its own choice of 7 (SGPR-limited): k_alloc_collect_ops 90 -> 86.5 us per frame (gpurun_out/s21)
+// (with the pre-test: 62 VGPRs, 83 SGPR spills, no scratch, still 8; profiles/alloc_pretest_ab.txt)
 constexpr int kAllocWpe = 8;
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAllocWpe))) void k_alloc_collect_ops(HashArgs A, BFDepthCameraParams cam, OpTable ops,
                                                            unsigned long long* __restrict__ cand, uint32_t candCap,
@@ -1592,6 +1696,7 @@ static HashArgs make_args(const SceneConfig& cfg, BFHashEntry* hash, uint32_t* h
     a.shardCount = cfg.shardCount;
     a.shardIndex = cfg.shardIndex;
     a.allocForceDirect = cfg.allocForceDirect;
+    a.allocNoPretest = cfg.allocNoPretest;
     a.shardChunk = cfg.shardChunk > 0 ? cfg.shardChunk : 1.0f;
     a.bitMask = bitMask;
     a.streamExtents = cfg.hp.streamingVoxelExtents;
@@ -1611,8 +1716,9 @@ SceneConfig scene_config(const BFHashParams& hp, const BFSceneOptions* so) {
         c.applyXcdRun = so->applyXcdRun;
         c.applyRounds = so->applyRounds;
         c.allocForceDirect = (so->testFlags & BF_SCENE_TEST_ALLOC_DIRECT) ? 1u : 0u;
+        c.allocNoPretest = (so->testFlags & BF_SCENE_TEST_ALLOC_NO_PRETEST) ? 1u : 0u;
         c.splatRowCap = so->splatRowCap;
-        BF_REQUIRE((so->testFlags & ~BF_SCENE_TEST_ALLOC_DIRECT) == 0, BF_ERR_ARG, "unknown BFSceneOptions.testFlags bits");
+        BF_REQUIRE((so->testFlags & ~(BF_SCENE_TEST_ALLOC_DIRECT | BF_SCENE_TEST_ALLOC_NO_PRETEST)) == 0, BF_ERR_ARG, "unknown BFSceneOptions.testFlags bits");
         BF_REQUIRE(so->applyXcdRun == 0 || ((so->applyXcdRun & (so->applyXcdRun - 1)) == 0 && so->applyXcdRun <= 32768u),
                    BF_ERR_ARG, "BFSceneOptions.applyXcdRun must be a power of two <= 32768");
         BF_REQUIRE(so->applyRounds <= 64, BF_ERR_ARG, "BFSceneOptions.applyRounds > 64");
@@ -1924,6 +2030,18 @@ BFTsdfStats Scene::stats() {
     std::memcpy(&s, sum, sizeof(s));
     s.pixels += hostPixels_;
     return s;
+}
+
+void Scene::allocPretestStats(uint64_t out[2]) {
+    std::vector<unsigned long long> h(STAT_SLOTS * STAT_FIELDS);
+    BF_HIP(hipMemcpyAsync(h.data(), stats_.p, stats_.bytes(), hipMemcpyDeviceToHost, stream_));
+    BF_HIP(hipStreamSynchronize(stream_));
+    static_assert(S_PRE_WALK < STAT_FIELDS && S_PRE_SKIP * 8 >= (int)sizeof(BFTsdfStats), "pre-test counters sit past BFTsdfStats");
+    out[0] = out[1] = 0;
+    for (int sl = 0; sl < STAT_SLOTS; sl++) {
+        out[0] += h[sl * STAT_FIELDS + S_PRE_SKIP];
+        out[1] += h[sl * STAT_FIELDS + S_PRE_WALK];
+    }
 }
 
 void Scene::resetStats() {

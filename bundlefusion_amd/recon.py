@@ -270,6 +270,12 @@ class Recon:
         check(lib().bf_recon_scene_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in BFTsdfStats._fields_}
 
+    def alloc_pretest_stats(self) -> dict:
+        """bf_recon_alloc_pretest_stats: alloc tiles the pre-test ended / that walked."""
+        out = (C.c_uint64 * 2)()
+        check(lib().bf_recon_alloc_pretest_stats(self.h, out))
+        return {"skipped": out[0], "walked": out[1]}
+
     def scene_capacity(self) -> dict:
         """bf_recon_scene_capacity: the scene's error bits, peak alloc candidates against the capacity, heap."""
         from .abi import BFSceneCapacity

@@ -73,10 +73,11 @@ typedef struct BFSceneOptions {
     /* v4: the voxel pass's scheduling (environment switches up to v3); 0 = the measured defaults */
     uint32_t applyXcdRun;       /* work-list positions handed to one XCD per run, a power of two (0 = 64) */
     uint32_t applyRounds;       /* grid of the voxel pass in rounds of resident workgroups (0 = 4) */
-    uint32_t testFlags;         /* test switches (0 in production): BF_SCENE_TEST_ALLOC_DIRECT */
+    uint32_t testFlags;         /* test switches (0 in production): BF_SCENE_TEST_ALLOC_DIRECT | _ALLOC_NO_PRETEST */
     uint32_t splatRowCap;       /* test switch: capacity of the ray-interval splat's row lists (0 = 4 per heap block) */
 } BFSceneOptions;
 #define BF_SCENE_TEST_ALLOC_DIRECT 1u  /* every walking alloc tile also takes the walk's congested path */
+#define BF_SCENE_TEST_ALLOC_NO_PRETEST 4u  /* no alloc tile ends at the block-box pre-test: every one walks (bit 2u stays unknown) */
 
 /* ctor + reset (CUDASceneRepHashSDF.h:32-34, :147-155 -> resetCUDA, CUDASceneRepHashSDF.cu:67) */
 int bf_scene_create(const BFHashParams* params, const BFSceneOptions* opts, bf_scene** out);
@@ -127,6 +128,10 @@ int bf_scene_error_flags(bf_scene* s, uint32_t* flags);
 int bf_scene_capacity(bf_scene* s, BFSceneCapacity* out);
 int bf_scene_get_stats(bf_scene* s, BFTsdfStats* out);
 int bf_scene_reset_stats(bf_scene* s);
+/* the alloc walk's pre-test since the last reset, in 16x16-pixel tiles per integrate op: out[0] ended by the pre-test
+ * (every block of the tile's box exists), out[1] went on into the walk. out[0] + out[1] = the tiles with a ray to
+ * walk. Synchronizes. */
+int bf_scene_alloc_pretest_stats(bf_scene* s, uint64_t out[2]);
 /* debugHash-style dump to HOST memory (CUDASceneRepHashSDF.h:179-314): any pointer may be NULL.
  * hash: BFHashEntry[4*numBuckets], heap: uint32[numSDFBlocks], voxels: BFVoxel[numSDFBlocks*512].
  * Entries carry the reference's ptr (heap block * 512), so a hash dump needs numSDFBlocks <= 2^22
@@ -412,6 +417,7 @@ int bf_recon_reintegrate(bf_recon* r);
 int bf_recon_synchronize(bf_recon* r);
 int bf_recon_stats(bf_recon* r, BFReconStats* out);
 int bf_recon_scene_stats(bf_recon* r, BFTsdfStats* out);
+int bf_recon_alloc_pretest_stats(bf_recon* r, uint64_t out[2]);  /* bf_scene_alloc_pretest_stats of the loop's scene */
 int bf_recon_reset_stats(bf_recon* r);  /* zero loop + scene counters and the device clocks */
 int bf_recon_heap_free_count(bf_recon* r, uint32_t* count);
 /* bf_scene_capacity of the loop's scene (waits for the scene stream). The loop checks the scene's error bits
