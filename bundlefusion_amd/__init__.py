@@ -144,9 +144,12 @@ class SceneRepHashSDF:
     """Mirror of CUDASceneRepHashSDF (DepthSensing/CUDASceneRepHashSDF.h:29-423) over bf_scene_*."""
 
     def __init__(self, params: BFHashParams, candidate_capacity=0, shard_count=1, shard_index=0, shard_chunk=1.0,
-                 test_flags=0, splat_row_cap=0):
+                 test_flags=0, splat_row_cap=0, apply_xcd_run=0, apply_rounds=0):
+        """apply_xcd_run / apply_rounds: the voxel pass's work-list run per XCD (a power of two up to 32768) and
+        its rounds of resident workgroups (up to 64); 0 takes the built-in values (64 and 4)."""
         self.params = params
         opts = BFSceneOptions(candidate_capacity, shard_count, shard_index, shard_chunk)
+        opts.applyXcdRun, opts.applyRounds = apply_xcd_run, apply_rounds
         opts.testFlags, opts.splatRowCap = test_flags, splat_row_cap
         self.h = C.c_void_p()
         check(lib().bf_scene_create(C.byref(params), C.byref(opts), C.byref(self.h)))

@@ -11,8 +11,9 @@ BOX_MAX = 256  # ALLOC_BOX_MAX (bundlefusion_amd/csrc/tsdf.hip)
 F = np.float32
 
 
-def ray_ends(T, depth, cam, params):
-    """(active [H, W] bool, id [H, W, 3], idEnd [H, W, 3]) of every pixel's ray."""
+def ray_ends(T, depth, cam, params, want_points=False):
+    """(active [H, W] bool, id [H, W, 3], idEnd [H, W, 3]) of every pixel's ray; with want_points also the
+    world end points rayMin, rayMax (float32 [H, W, 3]) the blocks were taken from."""
     H, W = cam.imageHeight, cam.imageWidth
     d = np.asarray(depth, F).reshape(H, W)
     maxd, tr, ts, vs = F(params.maxIntegrationDistance), F(params.truncation), F(params.truncScale), F(params.virtualVoxelSize)
@@ -29,16 +30,18 @@ def ray_ends(T, depth, cam, params):
 
         def block(depth_):
             v = [(depth_ * cx).astype(F), (depth_ * cy).astype(F), depth_]
-            out = []
+            out, pts = [], []
             for r in range(3):
                 w = (((e[r, 0] * v[0]).astype(F) + (e[r, 1] * v[1]).astype(F)).astype(F) + (e[r, 2] * v[2]).astype(F)).astype(F)
                 w = (w + (e[r, 3] * F(1.0))).astype(F)
+                pts.append(np.broadcast_to(w, d.shape))
                 p = (w / vs).astype(F)
                 q = (p + np.sign(p).astype(F) * F(0.5)).astype(F)
                 out.append(np.floor_divide(np.trunc(q).astype(np.int64), 8))  # v < 0: (v - 7) / 8 truncated
-            return np.stack(out, axis=-1)
+            return np.stack(out, axis=-1), np.stack(pts, axis=-1)
 
-        return active, block(lo), block(hi)
+        (b0, p0), (b1, p1) = block(lo), block(hi)
+        return (active, b0, b1, p0, p1) if want_points else (active, b0, b1)
 
 
 def ray_boxes(active, b0, b1):

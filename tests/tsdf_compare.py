@@ -69,7 +69,11 @@ class Pair:
     def __init__(self, params, cam, **scene_opts):
         self.params, self.cam = params, cam
         self.gpu = bfa.SceneRepHashSDF(params, **scene_opts)
-        self.ora = OracleScene(params)
+        # a sharded HIP scene is compared with an oracle scene owning the same chunks
+        shard = None
+        if scene_opts.get("shard_count", 1) > 1:
+            shard = (scene_opts["shard_count"], scene_opts.get("shard_index", 0), scene_opts.get("shard_chunk", 1.0))
+        self.ora = OracleScene(params, shard=shard)
         self._dev = {}
 
     def _upload(self, key, d, c):
