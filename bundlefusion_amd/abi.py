@@ -279,6 +279,10 @@ class BFBundlerRetry(C.Structure):  # what the last fuse_submap / retry did abou
         ("seeds", (C.c_uint32 * 2) * 5), ("reserved", C.c_uint32)]
 
 
+class BFBundlerEnd(C.Structure):  # what bf_bundling_end_sequence did about the trailing partial submap
+    _fields_ = [(n, C.c_uint32) for n in ("closed", "submap", "numFrames", "numCorr", "isValid")] + [("reserved", C.c_uint32 * 3)]
+
+
 class BFReconBundling(C.Structure):  # include/bf/types.h: what the loop did with an attached bundler
     _fields_ = [(n, C.c_uint64) for n in ("frames", "framesNotIntegrated", "submapsFused", "submapsInvalidEarly",
                                           "submapsInvalidVerified", "keyframesLost", "keyframesCleared")] + [
@@ -294,6 +298,7 @@ assert C.sizeof(BFMatchVerifyOptions) == 32
 assert C.sizeof(BFSiftOptions) == 48
 assert C.sizeof(BFBundlerFrame) == 168
 assert C.sizeof(BFBundlerRetry) == 80
+assert C.sizeof(BFBundlerEnd) == 32
 assert C.sizeof(BFReconBundling) == 64
 
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import DeviceArray, check, lib
-from .abi import (BUNDLER_GLOBAL, BUNDLER_LOCAL, BUNDLER_NO_FRAME, BUNDLER_OPT_LOCAL, ENTRYJ_DTYPE, BFBundlerFrame,
+from .abi import (BUNDLER_GLOBAL, BUNDLER_LOCAL, BUNDLER_NO_FRAME, BUNDLER_OPT_LOCAL, ENTRYJ_DTYPE, BFBundlerEnd, BFBundlerFrame,
                   BFBundlerKeyframe, BFBundlerOptions, BFBundlerRetry, BFBundlerStats, BFBundlerSubmap, BFCacheOptions, BFMatcherOptions,
                   BFMatchVerifyOptions, BFSiftOptions)
 from .cache import CUDACache
@@ -105,6 +105,15 @@ class Bundler:
         d["capacity"] = rc == -3
         return d
 
+    def end_sequence(self) -> dict:
+        """The end of the input (bf_bundling_end_sequence): a current local set of two or more images closes where it
+        stands and submap() / fuse_submap() / invalid_submap() take it as a full one; otherwise nothing closes. Afterwards
+        process_frame raises BF_ERR_STATE until reset(). Waits for nothing. dict(closed, submap, numFrames, numCorr,
+        isValid), all 0 when nothing closed."""
+        e = BFBundlerEnd()
+        check(lib().bf_bundling_end_sequence(self.h, C.byref(e)))
+        return {n: int(getattr(e, n)) for n in ("closed", "submap", "numFrames", "numCorr", "isValid")}
+
     def debug_reclose(self) -> dict:
         r = BFBundlerFrame()
         check(lib().bf_bundler_debug_reclose(self.h, C.byref(r)))
@@ -123,8 +132,8 @@ class Bundler:
         return s
 
     def submap(self) -> dict:
-        """The last closed submap, read back: corr (EntryJ), key_idx [n, 2], valid [frames], is_valid, frames, submap,
-        released, cache_frames (BFCachedFrame list), raw (the BFBundlerSubmap with its device pointers)."""
+        """The last closed submap (a boundary frame's, or the partial one end_sequence closed), read back: corr (EntryJ),
+        key_idx [n, 2], valid [frames], is_valid, frames, submap, released, cache_frames (BFCachedFrame list), raw (the BFBundlerSubmap with its device pointers)."""
         s = self.submap_raw()
         self.synchronize()
         n = s.numCorr

@@ -213,6 +213,7 @@ int bf_abi_struct_size(const char* name, size_t* out) {
         {"BFBundlerKeyframe", sizeof(BFBundlerKeyframe)},
         {"BFBundlerStats", sizeof(BFBundlerStats)},
         {"BFBundlerRetry", sizeof(BFBundlerRetry)},
+        {"BFBundlerEnd", sizeof(BFBundlerEnd)},
         {"BFReconBundling", sizeof(BFReconBundling)}};
     for (const auto& e : kSizes)
         if (std::strcmp(e.n, name) == 0) {
@@ -1623,6 +1624,12 @@ int bf_bundler_process_frame(bf_bundler* b, const uint8_t* d_color, uint32_t col
         ~Refresh() { bundler_refresh(h); }
     } refresh{b};
     b->b->processFrame(d_color, colorW, colorH, d_depthFilt, d_depthRaw, out);
+    BF_CATCH
+}
+int bf_bundling_end_sequence(bf_bundler* b, BFBundlerEnd* out) {
+    BF_TRY
+    BF_REQUIRE(b, BF_ERR_ARG, "null bundler");
+    b->b->endSequence(out);  // no swap: the borrowed handles stay as they are
     BF_CATCH
 }
 int bf_bundler_set_complete_trajectory(bf_bundler* b, const float* d_T, uint32_t n, uint32_t lastValidCompleteTransform) {

@@ -6,7 +6,8 @@
 //
 // Host wait budgets (counted in BFBundlerStats.hostWaits): processFrame <= 2 (the detector's key count; the closing
 // launch's record), fuseSubmap <= 2 (the fuse's count read-back; the record) and <= 3 with a retry attempt (the
-// candidate's record), retry <= 1, invalidSubmap 0.
+// candidate's record), retry <= 1, invalidSubmap 0, endSequence 0 (the valid flags' upload is stream-ordered; whoever reads
+// the closed submap on another stream waits, as after a boundary frame).
 //
 // Retry (Bundler::tryRevalidation, Bundler.cpp:306-352; SIFTImageManager.h:263-271; off unless setRetry): a key frame with
 // keys that matched no earlier one waits on a host deque, front in / front out; a key frame that matched pops one
@@ -68,6 +69,9 @@ public:
     void reset();
     void processFrame(const uint8_t* color, uint32_t cw, uint32_t ch, const float* depthFilt, const float* depthRaw,
                       BFBundlerFrame* out);
+    // processInput's past-the-end branch (OnlineBundler.cpp:171-174) -> prepareLocalSolve(curFrame, true) (:134-165): the
+    // current local set closes where it stands, nothing is copied into the other set; processFrame is refused afterwards
+    void endSequence(BFBundlerEnd* out);
     void setCompleteTrajectory(const float* T, uint32_t n, uint32_t lastValid);
     void submap(BFBundlerSubmap* out) const;
     void fuseSubmap(const float* localTransforms, BFBundlerKeyframe* out);
@@ -92,8 +96,14 @@ public:
     const BFBundlerStats& stats() const { return stats_; }
     uint32_t numFrames() const { return frame_; }      // frames processed since create / reset
     bool retryEnabled() const { return retry_; }
+    // the global cache's device table of BFCachedFrame [maxKeyframes]: key frame k's cache frame (the dense end solve's)
+    const BFCachedFrame* globalCacheTable() const { return frameTab_[2].p; }
 
 private:
+    // prepareLocalSolve's bookkeeping for set cur_ as the closed submap: the valid flags from the matcher's host mirror,
+    // uploaded on the stream
+    void recordClosed(uint32_t numFrames, uint32_t submap);
+
     // one launch of k_frame_close for image `cur` of matcher m on list `list` (0 / 1 local, 2 global), then the wait
     // over prev in [start, n)
     void closeFrame(Matcher& m, uint32_t list, uint32_t cur, uint32_t start, bool chain, uint32_t frameAll);
@@ -130,6 +140,7 @@ private:
     uint32_t cur_ = 0;            // which local set is m_local
     bool free_[2] = {true, true}; // the set is reset and empty
     uint32_t frame_ = 0;          // frames processed
+    bool ended_ = false;          // endSequence was called: no more frames until reset
     uint32_t lastValidComplete_ = 0;
     uint32_t seq_ = 0;
     const float* lastIntensity_ = nullptr;

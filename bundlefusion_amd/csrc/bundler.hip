@@ -403,6 +403,7 @@ void Bundler::reset() {
     total_[0] = total_[1] = total_[2] = 0;
     cur_ = 0;
     frame_ = 0;
+    ended_ = false;
     lastValidComplete_ = 0;
     lastIntensity_ = nullptr;
     closed_ = -1;
@@ -460,6 +461,7 @@ void Bundler::processFrame(const uint8_t* color, uint32_t cw, uint32_t ch, const
     BF_REQUIRE(color && depthFilt && depthRaw && out, BF_ERR_ARG, "process_frame: null argument");
     BF_REQUIRE(cw >= 2 && ch >= 2 && cw <= 16384 && ch <= 16384, BF_ERR_ARG, "process_frame: colour size");
     const uint32_t S = cfg_.submapSize, f = frame_;
+    BF_REQUIRE(!ended_, BF_ERR_STATE, "process_frame: the sequence is over (end_sequence); reset starts a new one");
     BF_REQUIRE(f < S * cfg_.maxKeyframes, BF_ERR_CAPACITY, "process_frame: submapSize * maxKeyframes frames have been processed");
     const bool closes = f > 0 && f % S == 0;  // isLastLocalFrame
     BF_REQUIRE(!closes || free_[1 - cur_], BF_ERR_STATE,
@@ -520,25 +522,55 @@ void Bundler::processFrame(const uint8_t* color, uint32_t cw, uint32_t ch, const
         loc_[o]->copyImageFrom(M, lf);
         cacheLoc_[o]->copyFrameFrom(C, lf);
         free_[o] = false;
-        closed_ = (int)cur_;
-        released_ = false;
-        closedFrames_ = lf + 1;
-        closedSubmap_ = out->submap;
-        closedCorr_ = total_[cur_];
-        closedValidImages_.resize(closedFrames_);
-        closedValid_ = false;
-        int32_t* hv = reinterpret_cast<int32_t*>(rec_ + 1) + (size_t)cur_ * (S + 1);
-        for (uint32_t i = 0; i < closedFrames_; i++) {
-            hv[i] = closedValidImages_[i] = M.valid(i);
-            if (i > 0 && M.valid(i)) closedValid_ = true;  // Bundler::isValid
-        }
-        BF_HIP(hipMemcpyAsync(dValid_[cur_].p, hv, closedFrames_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        recordClosed(lf + 1, out->submap);
         cur_ = o;
     } else {
         canReclose_ = lf > 0;
     }
     lastFrame_ = *out;
     BF_REQUIRE(!overflow, BF_ERR_CAPACITY, "process_frame: the frame's residuals would pass maxLocalCorr; none was appended");
+}
+
+void Bundler::recordClosed(uint32_t numFrames, uint32_t submap) {
+    const uint32_t S = cfg_.submapSize;
+    const Matcher& M = *loc_[cur_];
+    closed_ = (int)cur_;
+    released_ = false;
+    closedFrames_ = numFrames;
+    closedSubmap_ = submap;
+    closedCorr_ = total_[cur_];
+    closedValidImages_.resize(closedFrames_);
+    closedValid_ = false;
+    int32_t* hv = reinterpret_cast<int32_t*>(rec_ + 1) + (size_t)cur_ * (S + 1);
+    for (uint32_t i = 0; i < closedFrames_; i++) {
+        hv[i] = closedValidImages_[i] = M.valid(i);
+        if (i > 0 && M.valid(i)) closedValid_ = true;  // Bundler::isValid
+    }
+    BF_HIP(hipMemcpyAsync(dValid_[cur_].p, hv, closedFrames_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+}
+
+// processInput past the end (OnlineBundler.cpp:171-174): no local solve pending and the last frame not a boundary frame
+// -> prepareLocalSolve(curFrame, true) (:134-165). Its "only the overlap frame" branch (:138-144) cannot be reached from
+// there: a set of one image follows a boundary frame (or is frame 0 alone), which :171-173 exclude.
+void Bundler::endSequence(BFBundlerEnd* out) {
+    BF_REQUIRE(out != nullptr, BF_ERR_ARG, "end_sequence: null output");
+    BF_REQUIRE(frame_ > 0, BF_ERR_STATE, "end_sequence: no frame has been processed");
+    std::memset(out, 0, sizeof(*out));
+    if (ended_) return;
+    const uint32_t S = cfg_.submapSize, last = frame_ - 1, n = loc_[cur_]->numImages();
+    const bool boundary = last > 0 && last % S == 0;  // isLastLocalFrame: that frame closed its submap itself
+    if (n >= 2 && !boundary) {
+        BF_REQUIRE(closed_ < 0 || released_, BF_ERR_STATE,
+                   "end_sequence: this call closes a submap and the previous one waits for fuse_submap / invalid_submap");
+        recordClosed(n, last / S);
+        out->closed = 1;
+        out->submap = closedSubmap_;
+        out->numFrames = closedFrames_;
+        out->numCorr = closedCorr_;
+        out->isValid = closedValid_ ? 1u : 0u;
+    }
+    canReclose_ = false;
+    ended_ = true;
 }
 
 void Bundler::debugReclose(BFBundlerFrame* out) {

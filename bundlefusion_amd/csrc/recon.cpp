@@ -553,7 +553,7 @@ void Recon::finish() {
     const uint32_t s = (numFrames_ - 1) / S, n = numFrames_ - s * S;
     // a last submap of one frame is only the previous submap's overlap frame, solved with it
     // (isLastLocalFrame skips prepareLocalSolve for it, OnlineBundler.cpp:170-172, OnlineBundler.h:42)
-    // with a bundler the trailing partial submap stays at its integration poses (the end-of-sequence phase is not attached)
+    // with a bundler the trailing partial submap stays at its integration poses: endSequence closes and solves it
     if (s != lastSubmapEnqueued_ && n >= 2 && !bundler_) endSubmap(s, n);
     synchronize();
 }
@@ -797,13 +797,13 @@ void Recon::globalSolveTail(Pending& P, uint32_t ncorr) {
 // One end-of-sequence global solve (OnlineBundler.cpp:171-197 + optimizeGlobal with isSequenceDone,
 // :373-398): every keyframe and correspondence, max-residual removal, optionally the dense depth term
 // of USE_GLOBAL_DENSE_AT_END (:177-189) over the keyframes' cache frames.
-void Recon::issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1) {
+void Recon::issueEndSolve(Pending& P, uint32_t ncorr, float wDense, const BFCachedFrame* cache, hipEvent_t t0, hipEvent_t t1) {
     std::vector<float> ws(opt_.globalNonLin, 1.0f), wd(opt_.globalNonLin, wDense), wc(opt_.globalNonLin, 0.0f);
     SolveArgs a = globalSolveArgs(P.numKeyframes, ncorr);
     a.wSparse = ws.data();
     a.wDenseDepth = wd.data();
     a.wDenseColor = wc.data();
-    a.cache = wDense > 0.0f ? dGlobalCache_.p : nullptr;
+    a.cache = wDense > 0.0f ? cache : nullptr;
     a.cacheW = opt_.cacheWidth;
     a.cacheH = opt_.cacheHeight;
     std::memcpy(a.intrinsics, opt_.cacheIntrinsics, sizeof(a.intrinsics));
@@ -816,7 +816,6 @@ void Recon::issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t
 }
 
 SolveResult Recon::endSolve(float wDense, float* ms) {
-    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the end-of-sequence phase is not part of the pose-free loop");
     synchronize();  // every submap result applied: the ring is empty
     const uint32_t S = opt_.submapSize;
     BF_REQUIRE(numFrames_ > 0, BF_ERR_STATE, "end solve before the first frame");
@@ -828,12 +827,20 @@ SolveResult Recon::endSolve(float wDense, float* ms) {
         return none;
     }
     const uint32_t last = lastSubmapEnqueued_, nk = last + 1;
+    if (bundler_) bundleEndSolveInputs(nk);
     const uint32_t ncorr = (last < globalPrefix_.size()) ? globalPrefix_[last] : globalCorrN_;
     SolveResult res{};
     res.skipped = 1;
     if (ms) *ms = 0.0f;
     if (nk < 2 || !globalCorr_ || ncorr == 0) return res;
-    if (wDense > 0.0f) {
+    const BFCachedFrame* denseCache = dGlobalCache_.p;
+    if (wDense > 0.0f && bundler_) {
+        // Bundler::fuseToGlobal's cache copies (the stream they ran on was waited for when the key frame was made); an
+        // invalid key frame's slot holds no frame and its valid flag keeps every pair with it out of the dense term
+        BF_REQUIRE(bundler_->cache(BF_BUNDLER_GLOBAL).numFrames() == nk, BF_ERR_INTERNAL,
+                   "dense end solve: the bundler's global cache does not hold one frame per key frame");
+        denseCache = bundler_->globalCacheTable();
+    } else if (wDense > 0.0f) {
         std::vector<BFCachedFrame> tab(nk);
         for (uint32_t k = 0; k < nk; k++) {
             tab[k] = frames_[k * S].cache;  // Bundler::fuseToGlobal keeps the submap's first frame
@@ -848,7 +855,7 @@ SolveResult Recon::endSolve(float wDense, float* ms) {
     BF_HIP(hipEventCreate(&t0));
     BF_HIP(hipEventCreate(&t1));
     try {
-        issueEndSolve(P, ncorr, wDense, t0, t1);
+        issueEndSolve(P, ncorr, wDense, denseCache, t0, t1);
         BF_HIP(hipEventSynchronize(P.done));
         if (ms) BF_HIP(hipEventElapsedTime(ms, t0, t1));
     } catch (...) {
@@ -1115,7 +1122,7 @@ void Recon::storeCacheFrame(uint32_t f) {
 
 BFEndSequenceResult Recon::endSequence(const BFEndSequenceOptions& o) {
     BFEndSequenceResult res{};
-    BF_REQUIRE(!bundler_, BF_ERR_STATE, "a bundler is attached: the end-of-sequence phase is not part of the pose-free loop");
+    BF_REQUIRE(!bundler_ || numFrames_ > 0, BF_ERR_STATE, "a bundler is attached: end of sequence before the first frame");
     synchronize();
     if (numFrames_ == 0) return res;
     const int32_t N = o.numSolveFramesBeforeExit;
@@ -1125,10 +1132,18 @@ BFEndSequenceResult Recon::endSequence(const BFEndSequenceOptions& o) {
     const uint32_t S = opt_.submapSize, last = (numFrames_ - 1) / S, n = numFrames_ - last * S;
     auto keyframeCaches = [&]() {
         if (lastSubmapEnqueued_ == 0xFFFFFFFFu) return false;
+        if (bundler_) return true;  // every fused key frame has its cache frame in the bundler's global cache
         for (uint32_t k = 0; k <= lastSubmapEnqueued_; k++)
             if (!frames_[k * S].cache.depth) return false;
         return true;
     };
+    // the bundler's half of p = 0 (OnlineBundler.cpp:171-174): its current local set closes where it stands, or nothing
+    // does; either way its sequence is over, and a second endSequence finds nothing new to close
+    BFBundlerEnd bundlerEnd{};
+    if (bundler_) {
+        HostMsTimer t(bst_.bundlerMs);
+        bundler_->endSequence(&bundlerEnd);
+    }
     for (uint32_t p = 0; p < cap; p++) {
         res.pastEndFrames = p + 1;
         if (N < 0 || (int64_t)p <= (int64_t)N) {
@@ -1136,6 +1151,10 @@ BFEndSequenceResult Recon::endSequence(const BFEndSequenceOptions& o) {
                 // prepareLocalSolve(curFrame, true) at the first past-the-end processInput, then process():
                 // the partial submap's local solve, fuseToGlobal and the global solve
                 const uint64_t before = st_.globalSolves;
+                if (bundler_) {
+                    BF_REQUIRE(bundlerEnd.closed && bundlerEnd.submap == last && bundlerEnd.numFrames == n, BF_ERR_INTERNAL,
+                               "the bundler's trailing partial submap is not the loop's");
+                }
                 endSubmap(last, n);
                 synchronize();
                 res.localSolved = 1;
@@ -1320,6 +1339,24 @@ bool Recon::bundleGlobal(Pending& P, LocalSet& B, bool earlyInvalid) {
     BF_HIP(hipStreamSynchronize(bundler_->stream()));
     loopInvalid_[s] = (*P.gate == 0 || lost) ? 1 : 0;
     return !lost;
+}
+
+// An end solve's inputs from the bundler's state rather than the loop's copies: the key-frame count, the global list with
+// its prefix, and the key frames' valid flags (the global store's, which bundleTrajectory keeps equal to what the solves
+// cleared; key frame 0 made by invalidSubmap stays flagged valid in the store, so the loop's own record of it counts too)
+void Recon::bundleEndSolveInputs(uint32_t nk) {
+    HostMsTimer t(bst_.bundlerMs);
+    BFEntryJ* corr = nullptr;
+    const uint32_t* prefix = nullptr;
+    uint32_t n = 0, k = 0;
+    bundler_->global(&corr, nullptr, &n, &prefix, &k);
+    Matcher& G = bundler_->matcher(BF_BUNDLER_GLOBAL);
+    BF_REQUIRE(k == nk && G.numImages() == nk, BF_ERR_INTERNAL, "the bundler's key frame count is not the loop's");
+    setGlobalCorrespondences(corr, n, prefix, k);
+    std::vector<int> valid(nk);
+    for (uint32_t i = 0; i < nk; i++) valid[i] = (G.valid(i) && !loopInvalid_[i]) ? 1 : 0;
+    BF_HIP(hipMemcpyAsync(dGlobalValid_.p, valid.data(), sizeof(int) * nk, hipMemcpyHostToDevice, baStream_));
+    BF_HIP(hipStreamSynchronize(baStream_));
 }
 
 // After apply(P) gave the queue its transforms: the same rows to the bundler (OnlineBundler.cpp:394-397), and the valid

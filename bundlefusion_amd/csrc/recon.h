@@ -120,7 +120,7 @@ private:
     void endSubmap(uint32_t s, uint32_t numFrames);
     uint32_t takeSlot(uint32_t submap, uint32_t numLocal, uint32_t numKeyframes, bool endSolve);  // the next ring slot
     void issueSubmap(Pending& P, bool haveCache);
-    void issueEndSolve(Pending& P, uint32_t ncorr, float wDense, hipEvent_t t0, hipEvent_t t1);
+    void issueEndSolve(Pending& P, uint32_t ncorr, float wDense, const BFCachedFrame* cache, hipEvent_t t0, hipEvent_t t1);
     SolveArgs globalSolveArgs(uint32_t nk, uint32_t ncorr) const;
     void globalSolveTail(Pending& P, uint32_t ncorr);
     void waitResult(Pending& P);  // until P's solves are done; the wait counts as hostWaitMs
@@ -279,6 +279,7 @@ private:
     // although the local solve passed (global tracking lost)
     bool bundleGlobal(Pending& P, LocalSet& B, bool earlyInvalid);
     void bundleTrajectory(const Pending& P, uint32_t optimized, bool localOk);  // setCompleteTrajectory + valid flags
+    void bundleEndSolveInputs(uint32_t nk);          // Bundler::global + the global store's valid flags -> an end solve's
 
     // recordOps: TrajectoryManager call trace
     std::vector<BFQueueEvent> qEvents_;

@@ -138,6 +138,8 @@ class Recon:
         check(lib().bf_recon_process_frame(self.h, C.c_uint32(f)))
 
     def finish(self):
+        """Solves a trailing partial submap and waits for everything in flight. With a bundler attached it only waits:
+        the trailing partial submap stays at its integration poses until end_sequence closes and solves it."""
         check(lib().bf_recon_finish(self.h))
 
     def reintegrate(self):
@@ -145,7 +147,9 @@ class Recon:
 
     def end_solve(self, dense_depth_weight: float = 0.0):
         """One end-of-sequence global solve (OnlineBundler.cpp:171-197, 373-398); 15 = the
-        USE_GLOBAL_DENSE_AT_END solve. Returns (result dict, device ms)."""
+        USE_GLOBAL_DENSE_AT_END solve. Returns (result dict, device ms). With a bundler attached the key frames, the
+        global list, the valid flags and the dense term's cache frames are the bundler's; BF_ERR_STATE before the
+        first frame. A trailing partial submap is end_sequence's to solve, not this call's."""
         r = BFSolveResult()
         ms = C.c_float()
         check(lib().bf_recon_end_solve(self.h, C.c_float(dense_depth_weight), C.byref(r), C.byref(ms)))
@@ -155,7 +159,10 @@ class Recon:
                      dense_frame_limit: int = 10000, dense_depth_weight: float = 15.0, max_past_end_frames: int = 0):
         """The render loop past the last frame (bf_recon_end_sequence: OnlineBundler.cpp:167-196, 373-408;
         DepthSensing.cpp:1114-1126): the last submap, s_numSolveFramesBeforeExit global solves (the last with
-        the dense term), then re-integration until the queue is empty. Returns the result as a dict."""
+        the dense term), then re-integration until the queue is empty. Returns the result as a dict.
+        With a bundler attached this is the pose-free loop's last call: the bundler closes its trailing partial submap
+        (Bundler.end_sequence), which is solved, fused and matched as a full one, and the end solves run on the
+        bundler's lists. BF_ERR_STATE before the first frame; process_frame raises BF_ERR_STATE afterwards."""
         o = BFEndSequenceOptions(int(num_solve_frames_before_exit), 0 if dense_at_end else 1, int(dense_frame_limit),
                                  float(dense_depth_weight), int(max_past_end_frames))
         r = BFEndSequenceResult()
@@ -176,7 +183,9 @@ class Recon:
 
     def attach_bundler(self, bundler):
         """The pose-free loop (bf_recon_attach_bundler; bundler: bundler.Bundler, borrowed, it must outlive the loop):
-        every frame's integration pose and every EntryJ list then come from the bundler. Synchronous loop only."""
+        every frame's integration pose and every EntryJ list then come from the bundler. Synchronous loop only.
+        Per frame set_frame, set_frame_bundling, process_frame; at the end of the input end_sequence (finish alone
+        leaves a trailing partial submap unsolved)."""
         check(lib().bf_recon_attach_bundler(self.h, bundler.h if bundler is not None else None))
         self._bundler = bundler
 

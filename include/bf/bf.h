@@ -35,7 +35,8 @@ extern "C" {
                              additive, still 4: key fusing (BFMatcherOptions.fuseMaxCorr in place of reserved[0],
                              bf_match_fuse_to_global, bf_match_fuse_tracks, bf_match_image_keys);
                              additive, still 4: the bundler (BFBundlerOptions, BFBundlerFrame, BFBundlerSubmap,
-                             BFBundlerKeyframe, BFBundlerStats, bf_bundler_*) */
+                             BFBundlerKeyframe, BFBundlerStats, bf_bundler_*);
+                             additive, still 4: the bundler's end of sequence (BFBundlerEnd, bf_bundling_end_sequence) */
 
 /* ---- runtime ------------------------------------------------------------- */
 int bf_abi_version(void);
@@ -397,6 +398,9 @@ int bf_recon_set_global_correspondences(bf_recon* r, BFEntryJ* corr, uint32_t n,
                                         uint32_t numKeyframes);
 int bf_recon_set_initial_pose(bf_recon* r, const float T0[16]);
 int bf_recon_process_frame(bf_recon* r, uint32_t f);
+/* Solves a trailing partial submap of two or more frames and waits for everything in flight. With a bundler attached
+ * (bf_recon_attach_bundler) it only waits: the trailing partial submap stays at its integration poses, and
+ * bf_recon_end_sequence is the call that closes and solves it. */
 int bf_recon_finish(bf_recon* r);
 /* One end-of-sequence global solve (OnlineBundler::processInput past the last frame, OnlineBundler.cpp:171-197,
  * then optimizeGlobal with isSequenceDone, :373-398): all keyframes, every global correspondence, max-residual
@@ -404,7 +408,11 @@ int bf_recon_finish(bf_recon* r);
  * USE_GLOBAL_DENSE_AT_END (GlobalBundlingState.h:9), the last with dense depth weight 15 (:177-189) — pass
  * denseDepthWeight 15 for that one (0: sparse only). The dense term reads each keyframe's cache frame (the
  * submap's first frame, Bundler::fuseToGlobal's copy). Waits for the solve; the new poses go to the
- * trajectory (the queue picks them up). out / ms (device time) may be NULL. */
+ * trajectory (the queue picks them up). out / ms (device time) may be NULL.
+ * With a bundler attached the key-frame count, the global list and its prefix and the key frames' valid flags are the
+ * bundler's (bf_bundler_global, the global store's flags), and the dense term reads the bundler's global cache table; a
+ * key frame made by bf_bundler_invalid_submap is excluded by its flag. It solves no trailing partial submap (that is
+ * bf_recon_end_sequence's p = 0). BF_ERR_STATE before the first frame. */
 int bf_recon_end_solve(bf_recon* r, float denseDepthWeight, BFSolveResult* out, float* ms);
 /* with recordOps: submap s's local trajectory (HOST float[16 * (submapSize + 1)]) and the global keyframe poses
  * and valid flags after its global solve (HOST float[16 * maxKeyframes], int[maxKeyframes]); *numLocal /
@@ -516,7 +524,12 @@ int bf_recon_frame_ready(bf_recon* r, uint32_t f, void* stream);
  *   then reintegrate(); from p >= N on, the loop stops when generateUpdateLists leaves no active op.
  * N = numSolveFramesBeforeExit (s_numSolveFramesBeforeExit, 30). N < 0 is the reference's -1: a global solve
  * every iteration and no exit check (OnlineBundler.cpp:175, DepthSensing.cpp:1116), so only maxPastEndFrames
- * ends the phase. maxPastEndFrames caps the iterations (0 = 100000). Waits for every solve (deterministic). */
+ * ends the phase. maxPastEndFrames caps the iterations (0 = 100000). Waits for every solve (deterministic).
+ * With a bundler attached the same schedule runs from the bundler's state: p = 0 calls bf_bundling_end_sequence and the
+ * partial submap it closed (if any) goes through the local solve, bf_bundler_fuse_submap / _invalid_submap, the global
+ * match, the gate and the global solve as a full submap does; "every keyframe has a cache frame" holds for the valid key
+ * frames of the bundler's global cache. Before the first frame: an empty result without a bundler, BF_ERR_STATE with
+ * one. Afterwards the bundler's sequence is over and bf_recon_process_frame returns its BF_ERR_STATE. */
 typedef struct BFEndSequenceOptions {
     int32_t numSolveFramesBeforeExit;  /* [30] */
     int32_t disableDenseAtEnd;         /* 1: no USE_GLOBAL_DENSE_AT_END switch */
@@ -825,7 +838,8 @@ int bf_sift_timer_stop(bf_sift* s, bf_timer* t, float* ms); /* synchronizes */
  *   bf_bundler_fuse_submap    <= 2: the fuse's count read-back, and the record (none for the first key frame);
  *                             <= 3 with retry on, when a candidate is tried: its record;
  *   bf_retry_attempt          <= 1: the candidate's record (none when there is nothing to do);
- *   bf_bundler_invalid_submap    0.
+ *   bf_bundler_invalid_submap    0;
+ *   bf_bundling_end_sequence     0.
  * tryRevalidation, the retry list and the global-only trajectory re-initialisation (Bundler.cpp:223-237, 306-352; the
  * reference's USE_RETRY) are OFF unless bf_retry_enable turns them on; with retry off every call behaves and waits
  * as it did before they existed. DESIGN.md §3.7 has the semantics and the departures. */
@@ -858,12 +872,28 @@ int bf_bundler_timer_stop(bf_bundler* b, bf_timer* t, float* ms); /* synchronize
  * frame is stored as an INVALID image (siftPose copied, integrateTransform -inf, *out filled) and the handle goes on. */
 int bf_bundler_process_frame(bf_bundler* b, const uint8_t* d_color, uint32_t colorW, uint32_t colorH, const float* d_depthFilt,
                              const float* d_depthRaw, BFBundlerFrame* out);
+/* The end of the input: processInput's past-the-end branch (OnlineBundler.cpp:171-174) -> prepareLocalSolve(curFrame,
+ * true) (OnlineBundler.cpp:134-165). With n images in the current local set (the overlap frame + the frames after it):
+ * n >= 2 and the last frame no boundary frame: the set closes where it stands (out->closed = 1). bf_bundler_submap then
+ * describes it with numFrames = n < submapSize + 1, and bf_bundler_fuse_submap / _invalid_submap take it as they take a
+ * full one; nothing is copied into the other set and the sets are not swapped (the borrowed BF_BUNDLER_LOCAL handles
+ * keep naming the closed set). n <= 1, or the last frame closed a submap itself: nothing closes
+ * (out->closed = 0; a closed submap that still waits stays as it is). The branch "only the overlap frame -> invalidate"
+ * (:138-144) cannot be reached from :171-174 and has no counterpart. After the call the sequence is over:
+ * bf_bundler_process_frame returns BF_ERR_STATE until bf_bundler_reset, a second call does nothing and reports closed = 0;
+ * bf_retry_attempt stays the sequence-over retry. Waits for nothing (the valid flags' upload is stream-ordered).
+ * *out (HOST, required) is filled. BF_ERR_ARG: a null argument. BF_ERR_STATE: no frame has been processed; or a set
+ * would close and the previous closed submap has not been taken by bf_bundler_fuse_submap / _invalid_submap (then
+ * nothing changed and the call may be repeated). Like bf_retry_*, it takes the bundler's handle under a prefix of its
+ * own: the set of bf_bundler_* names is the handle's first surface and stays as it was. */
+int bf_bundling_end_sequence(bf_bundler* b, BFBundlerEnd* out);
 /* The two inputs of computeSiftTransformCU that the global solve produces (OnlineBundler.cpp:126-129): d_T DEVICE
  * float[n][16] is copied (stream-ordered) into the handle's completeTrajectory; n <= submapSize * maxKeyframes and
  * lastValidCompleteTransform < max(n, 1), else BF_ERR_ARG. After create / reset: lastValidCompleteTransform = 0. */
 int bf_bundler_set_complete_trajectory(bf_bundler* b, const float* d_T, uint32_t n, uint32_t lastValidCompleteTransform);
 /* The last closed submap (Bundler::isValid, getValidImages, the EntryJ list, the cache table). Its pointers stay valid
- * and its contents unchanged until the next submap closes. BF_ERR_STATE: no submap has closed. */
+ * and its contents unchanged until the next submap closes. numFrames is submapSize + 1, or fewer for the partial submap
+ * bf_bundling_end_sequence closed. BF_ERR_STATE: no submap has closed. */
 int bf_bundler_submap(bf_bundler* b, BFBundlerSubmap* out);
 /* OnlineBundler::processGlobal, state PROCESS (OnlineBundler.cpp:302-348): fuseToGlobal of the closed submap with the
  * solved d_localTransforms (DEVICE float[numFrames][16], frame -> the submap's first frame) = bf_match_fuse_to_global +
@@ -946,9 +976,20 @@ int bf_retry_debug_close(bf_bundler* b, uint32_t idx, BFBundlerRetry* out);
  * cacheIntrinsics; the bundler's maxLocalCorr / maxGlobalCorr above the loop's. BF_ERR_STATE: a frame has been processed
  * (by the loop or by the bundler); a communicator, a cache or a preprocessor is attached; retry is enabled on the
  * bundler; bf_recon_set_initial_pose was called (the bundler's trajectory starts at the identity); a bundler is attached
- * already. Once attached, bf_recon_set_comm, _attach_cache, _attach_preproc, _set_initial_pose, _end_solve and
- * _end_sequence return BF_ERR_STATE, bf_recon_set_frame's Tinc and cache are ignored, and bf_recon_finish leaves a
- * trailing partial submap at its integration poses. */
+ * already. Once attached, bf_recon_set_comm, _attach_cache, _attach_preproc and _set_initial_pose return BF_ERR_STATE,
+ * and bf_recon_set_frame's Tinc and cache are ignored.
+ *
+ * The end of the input: bf_recon_end_sequence runs the whole end-of-sequence phase from the bundler's state. At p = 0 it
+ * calls bf_bundling_end_sequence, and a trailing partial submap (2 .. submapSize images) takes the path a full one takes:
+ * local solve over the bundler's list, fuse or invalidate, global match, the gate, the global solve, the complete
+ * trajectory back to the bundler. The past-the-end global solves (bf_recon_end_solve) take the key-frame count, the
+ * global list with its prefix, the key frames' valid flags and, for the dense solve, the global cache's device table
+ * from the bundler; a key frame the bundler holds invalid is excluded by its flag. Before the first frame both calls
+ * return BF_ERR_STATE; after bf_recon_end_sequence, bf_recon_process_frame fails with the bundler's BF_ERR_STATE.
+ * bf_recon_finish does NOT solve a trailing partial submap when a bundler is attached: its frames stay at their
+ * integration poses until bf_recon_end_sequence. One departure from the reference: the partial submap's key frame goes
+ * through the gate as every key frame does, where optimizeGlobal forces PROCESS once the sequence is over
+ * (OnlineBundler.cpp:380); the loop without a bundler does not force it either. */
 int bf_recon_attach_bundler(bf_recon* r, bf_bundler* b);
 /* Frame f's three bundling images, as bf_bundler_process_frame takes them (copyToBundling's). They are read on the
  * bundler's stream inside bf_recon_process_frame(f): complete when that call is made, valid until it returns (frame 0:

@@ -417,6 +417,14 @@ typedef struct BFBundlerRetry {
     uint32_t reserved;
 } BFBundlerRetry;
 
+/* What bf_bundling_end_sequence did about the trailing partial submap (HOST). */
+typedef struct BFBundlerEnd {
+    uint32_t closed;                   /* 1: the current local set closed where it stood, bf_bundler_submap describes it */
+    uint32_t submap, numFrames;        /* its index and its images (the overlap frame + the frames after it); 0 when !closed */
+    uint32_t numCorr, isValid;         /* its list's length and Bundler::isValid; 0 when !closed */
+    uint32_t reserved[3];
+} BFBundlerEnd;
+
 typedef struct BFBundlerStats {
     uint64_t frames;       /* bf_bundler_process_frame calls that reached the device */
     uint64_t hostWaits;    /* times the host waited for the stream inside process_frame / fuse_submap / invalid_submap / bf_retry_* */
@@ -441,6 +449,7 @@ typedef struct BFReconBundling {
 static_assert(sizeof(BFSiftOptions) == 48, "BFSiftOptions is 48 B");
 static_assert(sizeof(BFBundlerFrame) == 168, "BFBundlerFrame is 168 B");
 static_assert(sizeof(BFBundlerRetry) == 80, "BFBundlerRetry is 80 B");
+static_assert(sizeof(BFBundlerEnd) == 32, "BFBundlerEnd is 32 B");
 static_assert(sizeof(BFReconBundling) == 64, "BFReconBundling is 64 B");
 static_assert(sizeof(BFSiftKeyPoint) == 16, "SIFTKeyPoint is 16 B");
 static_assert(sizeof(BFMatchVerifyOptions) == 32, "BFMatchVerifyOptions is 32 B");
